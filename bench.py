@@ -7,12 +7,17 @@ main tree commits (Circle-FFT LDE + Blake2s Merkle) -> lookup elements -> REAL l
 decommit -> proof bytes on the host; everything resident in HBM (the trace is generated on device).
 `value` = 2^log_n_rows * steps / seconds (max over ranks).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-rows 22] [--no-cpu-baseline] [--no-v1-shaped] [--one-proof]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-rows 22] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-v1-shaped]] [--one-proof]
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the line can carry, each after the
+timed steps: the instrumented prove behind stages_ms / roofline / merkle (/ xgmi), the v1-shaped workload, the host-resident trace,
+the preprocessed-tree reuse, the CPU baseline, and for N > 1 the extra row-sharded attempt ("one_proof").
+--dump-outputs DIR: rank 0 writes the proof words of the last timed step to DIR/proof_words.npy (float64, exact for u32); the seeds
+are fixed, so the same arguments give the same file.
 For N > 1 it runs one rank per GPU over RCCL: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N ...`, or — started PLAINLY as `python bench.py --gpus N` (no WORLD_SIZE in the environment) — it starts those N ranks by
 itself (self_launch below: the same torch.distributed.run command on 127.0.0.1 and a free port; the line says so in "launcher").
 Default for N > 1: one independent proof of the 2^22-row trace per GPU (batch throughput, "scaling": "weak") as `value`;
-the same run then ALSO tries ONE row-sharded proof on the N GPUs and reports it in the "one_proof" block (strong scaling, bytes over
+with --full the same run then ALSO tries ONE row-sharded proof on the N GPUs and reports it in the "one_proof" block (strong scaling, bytes over
 xGMI, equality with the single-GPU proof) — guarded so that no failure or hang there can cost the headline line.
 --one-proof: the N GPUs prove ONE trace together (row-sharded prove, "strong" — DESIGN.md §7); that path is byte-exact on thread
 ranks and over gloo but has never run on more than one physical GPU (this pool has one per box), so it is opt-in until it has: the
@@ -134,7 +139,12 @@ def main():
     ap.add_argument("--transport", default=None, choices=["rccl-native", "torch"],
                     help="--one-proof: who carries the collectives — the library's own RCCL transport (csrc/comm_rccl.hip, the default with --backend nccl) or the torch.distributed callbacks")
     ap.add_argument("--same-device", action="store_true", help="testing only: every rank on GPU 0 (RCCL refuses that; use with --backend gloo)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure everything besides the headline (instrumented prove, v1 shape, host trace, "
+                    "preprocessed reuse, CPU baseline, N > 1: the one-proof attempt); the --no-* switches trim this")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the proof words of the last timed step to DIR/proof_words.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started plainly (the form the driver uses for N = 1): this process becomes the launcher of the N ranks
@@ -207,14 +217,14 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for s in range(steps):
-            prove(cs, cf, 2000 + s)
+            words = prove(cs, cf, 2000 + s)
         barrier()
         el = time.perf_counter() - t0
         if dist is not None:
             t = torch.tensor([el], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        return el
+        return el, words
 
     one_proof_equal = None
     if sharded:
@@ -228,12 +238,18 @@ def main():
         one_proof_equal = bool(int(ok.item()))
         if not one_proof_equal:
             raise SystemExit("bench.py --one-proof: a rank's row-sharded proof differs from the single-GPU proof")
-    elapsed = timed(comps, cfg, args.steps, args.warmup)
-    # one extra instrumented step (outside the timed region) for the per-stage split and the FFT roofline
-    words, stats = prove(comps, cfg, 4242, want_stats=True)
+    elapsed, last_words = timed(comps, cfg, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "proof_words.npy"), np.asarray(last_words, dtype=np.float64))
+    stats = None
+    if args.full:
+        # one extra instrumented step (outside the timed region) for the per-stage split and the FFT roofline
+        words, stats = prove(comps, cfg, 4242, want_stats=True)
 
     v1 = None
-    if not args.no_v1_shaped and world == 1 and not args.legacy_synth:
+    if args.full and not args.no_v1_shaped and world == 1 and not args.legacy_synth:
         # The reference's v1 machine shape: LOG_CONSTRAINT_DEGREE = 2 (reference prover/src/components/mod.rs:12: the
         # constraints are evaluated on a 2^(n+2) domain, every column re-evaluated there; twiddles for n+3, machine.rs:186-194),
         # ~250 logup columns ~ 1.0 k interaction base columns (chips/range_check/range256.rs:271-288 et al.), 8 extension components
@@ -245,7 +261,7 @@ def main():
             v1_comps = [(args.log_rows, args.n_pre, args.n_main, 4 * args.v1_logup, 2)] + [(8 + k, 2, 6 + k, 4, 1) for k in range(8)]
             v1_cfg = nz.default_config(pow_bits=args.pow_bits, hash_mode=args.hash_mode, log_constraint_degree=2)
             v1_steps = max(1, min(2, args.steps))
-            v1_el = timed(v1_comps, v1_cfg, v1_steps, 1)
+            v1_el, _ = timed(v1_comps, v1_cfg, v1_steps, 1)
             v1_words, v1_stats = prove(v1_comps, v1_cfg, 4243, want_stats=True)
             n_cols = sum(c[1] + c[2] + c[3] for c in v1_comps)
             v1 = {"workload": "v1-shaped: 2^%d rows, %d preprocessed + %d main + %d interaction columns (%d logup columns), log_constraint_degree bound 2 for the main component (its main-trace constraints are degree 4, its logup constraints degree 2 like finalize_logup's: degree-aware composition, DESIGN.md §6 item 22), 1 for the 8 extension components of 2^8..2^15 rows"
@@ -261,7 +277,7 @@ def main():
             # logup constraints of the reference's shape cost
             try:
                 t_comps = [v1_comps[0] + (nz.TUPLES_V1,)] + v1_comps[1:]
-                t_el = timed(t_comps, v1_cfg, v1_steps, 1)
+                t_el, _ = timed(t_comps, v1_cfg, v1_steps, 1)
                 _, t_stats = prove(t_comps, v1_cfg, 4244, want_stats=True)
                 v1["reference_tuple_widths"] = {"what": "main component with NX_TUPLES_V1 (tuple widths 1, 1, 4, 1, 9, 1, 3, 1 cycling; constant and column-sum entries; +1 / -m / +m numerators)",
                                                 "ms_per_step": 1e3 * t_el / v1_steps, "value": (1 << args.log_rows) * v1_steps / t_el, "unit": "cycles/s",
@@ -275,7 +291,7 @@ def main():
     # HBM; this block times the same proof from a host-resident preprocessed + main trace, uploaded chunk by chunk UNDER the commits' own
     # transforms (nx_prove_machine_host).  PCIe-inclusive, reported next to the headline, never as `value`.
     host_trace = None
-    if world == 1 and not args.no_host_trace and not args.legacy_synth:
+    if args.full and world == 1 and not args.no_host_trace and not args.legacy_synth:
         try:
             import numpy as np
             hseed = 2000
@@ -321,12 +337,12 @@ def main():
     # "machine.reuse_preprocessed" the tree of the first proof is adopted by the later ones (nx_prover_tree_adopt's rule; same proof bytes).
     # Informational — `value` always commits every tree afresh, as the reference does.
     pre_reuse = None
-    if world == 1 and not args.legacy_synth:
+    if args.full and world == 1 and not args.legacy_synth:
         try:
             import numpy as np
             be.set_option("machine.reuse_preprocessed", 1)
             rsteps = max(1, min(3, args.steps))
-            r_el = timed(comps, cfg, rsteps, 1)
+            r_el, _ = timed(comps, cfg, rsteps, 1)
             same = bool(np.array_equal(be.prove_machine(comps, cfg, seed=4242), words))
             pre_reuse = {"ms_per_step": 1e3 * r_el / rsteps, "value": (1 << args.log_rows) * rsteps / r_el, "unit": "cycles/s", "steps": rsteps, "equals_fresh_commit_proof": same,
                          "what": "the %d preprocessed columns' tree committed once and adopted by the following proofs (seeds differ: main and interaction trees are new every time)" % args.n_pre}
@@ -348,7 +364,6 @@ def main():
     if rank == 0:
         n_cycles = (1 << args.log_rows) * args.steps * (1 if sharded else world)
         n_cols_total = args.n_pre + args.n_main + n_inter
-        roof = lde_roofline(stats, args.log_rows, n_cols_total)
         out = {
             "metric": "RISC-V cycles proved/sec at log_n_rows=%d; achieved HBM GB/s on Circle-FFT" % args.log_rows,
             "value": n_cycles / elapsed,
@@ -370,24 +385,28 @@ def main():
                        "log_n_rows": args.log_rows,
                        "parallelism": ("ONE proof on %d GPUs: column-parallel LDE, all-to-all into row blocks, local hashing / constraints / quotients / FRI folds" % world) if sharded
                        else ("1 independent proof per GPU" if world > 1 else "1 GPU"),
-                       "proof_words": int(len(words)),
+                       "proof_words": int(len(last_words)),
                        # every byte of the proof is Stwo's: these only choose WHERE exact polynomial identities let the prover read fewer bytes
                        # (0 = Stwo's evaluation order, same proof; profiles/r03_*_ab.log have both)
                        "prover_options": prover_options},
-            "roofline": roof,
-            # the FFT is VALU-issue bound on gfx950, not HBM bound: butterflies of one prove's iFFT + LDE work
-            # (n/2 * N per iFFT, n * N per 2x LDE: the trivial top layer is not computed) against the measured chip ceiling of the
-            # butterfly instruction sequence itself (tools/ubench/bfly_rates.hip, variant B: 4.73e12 butterflies/s)
-            "roofline_valu": (lambda nb: {"bound": "valu", "achieved": nb / (stats["lde_kernel_ms"] * 1e-3) / 1e12, "peak": 4.73, "unit": "T butterflies/s",
-                                          "frac": nb / (stats["lde_kernel_ms"] * 1e-3) / 4.73e12, "butterflies": nb})(
-                ((n_cols_total * 1.5 * args.log_rows * (1 << args.log_rows)) / (world if sharded else 1)
-                 + 4 * ((args.log_rows + 1) / 2.0 + (args.log_rows + 1)) * (2 << args.log_rows))) if stats["lde_kernel_ms"] > 0 else None,
-            "stages_ms": {k: round(stats[k], 3) for k in STAGES},
-            "merkle": {"kernel_ms": stats["merkle_kernel_ms"], "algorithmic_bytes": stats["merkle_algorithmic_bytes"],
-                       "achieved_GBs": stats["merkle_algorithmic_bytes"] / (stats["merkle_kernel_ms"] * 1e-3) / 1e9 if stats["merkle_kernel_ms"] > 0 else 0.0},
         }
+        if stats is not None:
+            out.update({
+                "roofline": lde_roofline(stats, args.log_rows, n_cols_total),
+                # the FFT is VALU-issue bound on gfx950, not HBM bound: butterflies of one prove's iFFT + LDE work
+                # (n/2 * N per iFFT, n * N per 2x LDE: the trivial top layer is not computed) against the measured chip ceiling of the
+                # butterfly instruction sequence itself (tools/ubench/bfly_rates.hip, variant B: 4.73e12 butterflies/s)
+                "roofline_valu": (lambda nb: {"bound": "valu", "achieved": nb / (stats["lde_kernel_ms"] * 1e-3) / 1e12, "peak": 4.73, "unit": "T butterflies/s",
+                                              "frac": nb / (stats["lde_kernel_ms"] * 1e-3) / 4.73e12, "butterflies": nb})(
+                    ((n_cols_total * 1.5 * args.log_rows * (1 << args.log_rows)) / (world if sharded else 1)
+                     + 4 * ((args.log_rows + 1) / 2.0 + (args.log_rows + 1)) * (2 << args.log_rows))) if stats["lde_kernel_ms"] > 0 else None,
+                "stages_ms": {k: round(stats[k], 3) for k in STAGES},
+                "merkle": {"kernel_ms": stats["merkle_kernel_ms"], "algorithmic_bytes": stats["merkle_algorithmic_bytes"],
+                           "achieved_GBs": stats["merkle_algorithmic_bytes"] / (stats["merkle_kernel_ms"] * 1e-3) / 1e9 if stats["merkle_kernel_ms"] > 0 else 0.0},
+            })
         if sharded:
             out["one_proof_equals_single_gpu"] = one_proof_equal
+        if sharded and stats is not None:
             out["xgmi"] = {"transport": transport, "bytes_sent_per_gpu_per_proof": int(stats["comm_bytes"]), "ms_in_collectives_per_proof": round(stats["comm_ms"], 3),
                            "collectives": "one all-to-all per trace tree (LDE columns -> row blocks), all-gather of W subtree roots per tree, of the columns read at a non-zero mask offset, of the composition accumulator and of the FRI tail; sampled / queried values (KBs)"}
         if host_trace is not None:
@@ -396,13 +415,13 @@ def main():
             out["preprocessed_reuse"] = pre_reuse
         if v1 is not None:
             out["config_v1_shaped"] = v1
-    # N > 1, default mode: `value` above is N independent proofs.  The SAME run then also tries ONE row-sharded proof on the N GPUs
+    # N > 1, default mode: `value` above is N independent proofs.  With --full the SAME run then also tries ONE row-sharded proof on the N GPUs
     #  and reports it in a block of its own: the strong-scaling number and the RCCL bring-up result of whatever
     # multi-GPU box the driver has, at no risk to the headline — every failure, on any rank, ends as {"error": ...}, and a collective
     # that never returns (a peer died before entering it) is cut off by a watchdog: the line is still printed, every rank still exits 0.
     one_proof = None
     hung = False
-    if world > 1 and not sharded and not args.no_one_proof and not args.legacy_synth:
+    if args.full and world > 1 and not sharded and not args.no_one_proof and not args.legacy_synth:
         import threading
         box = {}
         # the attempt drives RCCL paths no 1-GPU box has ever run: if THIS process dies in it (a fault inside a collective, or the launcher
@@ -458,7 +477,7 @@ def main():
     if rank == 0:
         if one_proof is not None:
             out["one_proof"] = one_proof
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             import oracle_lib as O   # checker / baseline only — never part of the measured GPU path
             import numpy as np
             O.build_oracle()

@@ -903,7 +903,7 @@ def test_bench_two_processes_one_proof(tmp_path):
         s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]
     env = dict(os.environ); env.pop("NX_FRI_DIST_MIN_LOG", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(root, "bench.py"), "--gpus", "2", "--one-proof", "--steps", "1", "--warmup", "1", "--log-rows", "14", "--backend", "gloo", "--same-device"],
+                        os.path.join(root, "bench.py"), "--gpus", "2", "--one-proof", "--steps", "1", "--warmup", "1", "--log-rows", "14", "--backend", "gloo", "--same-device", "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -914,7 +914,7 @@ def test_bench_two_processes_one_proof(tmp_path):
     assert out["one_proof_equals_single_gpu"] is True      # the first-contact check every --one-proof run makes
     # the default for N > 1: one independent proof per GPU
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port + 1 if port < 65000 else port - 1),
-                        os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--log-rows", "14", "--backend", "gloo", "--same-device"],
+                        os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--log-rows", "14", "--backend", "gloo", "--same-device", "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -927,21 +927,22 @@ def test_bench_two_processes_one_proof(tmp_path):
     # collective — an error or the watchdog — and the headline line still comes out, exit code 0
     env2 = dict(env); env2["NX_BENCH_ONE_PROOF_FAULT"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port + 2 if port < 65000 else port - 2),
-                        os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--log-rows", "14", "--backend", "gloo", "--same-device", "--one-proof-timeout", "20"],
+                        os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--log-rows", "14", "--backend", "gloo", "--same-device", "--one-proof-timeout", "20", "--full"],
                        cwd=root, env=env2, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert out["value"] > 0 and out["scaling"] == "weak" and "error" in out["one_proof"]
 
 
-def test_bench_started_plainly_with_gpus_2_launches_its_own_ranks():
+def test_bench_started_plainly_with_gpus_2_launches_its_own_ranks(be, nz, tmp_path):
     """`python bench.py --gpus 2` with no launcher around it (the form the driver uses for N = 1) starts the 2 ranks by
     itself — the JSON line says n_gpus 2 and names the launcher — instead of silently benchmarking one GPU; the N = 1 line is
-    unchanged apart from the new "launcher" key."""
+    unchanged apart from the new "launcher" key.  A plain N = 1 run carries the headline only, and --dump-outputs writes the proof of
+    its last timed step (seed 2000 + steps - 1): the library's own proof of that statement, word for word."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "NX_FRI_DIST_MIN_LOG", "NX_BENCH_LAUNCHER")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--log-rows", "14", "--backend", "gloo", "--same-device"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--log-rows", "14", "--backend", "gloo", "--same-device", "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -949,11 +950,17 @@ def test_bench_started_plainly_with_gpus_2_launches_its_own_ranks():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["launcher"].startswith("self") and out["value"] > 0
     assert "error" not in out["one_proof"] and out["one_proof"]["equals_single_gpu"] is True
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--log-rows", "14", "--no-cpu-baseline", "--no-v1-shaped", "--no-host-trace"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--log-rows", "14", "--no-cpu-baseline", "--no-v1-shaped", "--no-host-trace",
+                        "--dump-outputs", str(tmp_path / "dump")],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["launcher"].startswith("none") and out["scaling"] == "strong" and "one_proof" not in out
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["higher_is_better"] is True and out["dtype"] == "u32 (M31)"
+    assert not {"stages_ms", "roofline", "preprocessed_reuse", "cpu_baseline"} & set(out)
+    dumped = np.load(tmp_path / "dump" / "proof_words.npy")
+    assert dumped.dtype == np.float64 and len(dumped) == out["config"]["proof_words"]
+    _same(be.prove_machine([(14, 27, 347, 64)], nz.default_config(pow_bits=10), seed=2001), dumped.astype(np.uint32))
 
 
 def test_torch_transport_on_device_buffers_nccl_world1(be, nz):

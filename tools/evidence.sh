@@ -13,6 +13,6 @@ run wide_logup_bench.py 20 32      # a wide logup AIR end to end through the ses
 run upload_bench.py 22 64          # host trace hand-over
 run many_components.py             # prover2-shaped statement (55 components)
 run concurrent_proves.py 22 2      # throughput mode
-for mode in 0 1; do echo "{\"tool\": \"bench.py\", \"args\": \"--hash-mode $mode --no-cpu-baseline --no-v1-shaped\", \"result\": $(timeout 300 python bench.py --hash-mode $mode --no-cpu-baseline --no-v1-shaped 2>/dev/null | tail -1)}" >> "$OUT"; done
-echo "{\"tool\": \"bench.py\", \"args\": \"--legacy-synth --no-cpu-baseline\", \"result\": $(timeout 300 python bench.py --legacy-synth --no-cpu-baseline 2>/dev/null | tail -1)}" >> "$OUT"
+for mode in 0 1; do echo "{\"tool\": \"bench.py\", \"args\": \"--full --hash-mode $mode --no-cpu-baseline --no-v1-shaped\", \"result\": $(timeout 300 python bench.py --full --hash-mode $mode --no-cpu-baseline --no-v1-shaped 2>/dev/null | tail -1)}" >> "$OUT"; done
+echo "{\"tool\": \"bench.py\", \"args\": \"--full --legacy-synth --no-cpu-baseline\", \"result\": $(timeout 300 python bench.py --full --legacy-synth --no-cpu-baseline 2>/dev/null | tail -1)}" >> "$OUT"
 cat "$OUT" | cut -c 1-400

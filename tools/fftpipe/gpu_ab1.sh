@@ -12,5 +12,5 @@ timeout 300 python tools/fft_tune.py 22 128 3 fft.pipe=0 fft.pipe=1 fft.pipe=1,f
 cat $O/sweep22.jsonl
 timeout 200 python tools/fft_tune.py 20 347 3 fft.pipe=0 fft.pipe=1 fft.pipe=1,fft.batch_cols=4 fft.pipe=1,fft.batch_cols=4,fft.streams=1 > $O/sweep20.jsonl 2>&1
 cat $O/sweep20.jsonl
-timeout 300 python bench.py --no-cpu-baseline --no-v1-shaped --steps 10 > $O/bench_pipe.json 2> $O/bench_pipe.err; tail -1 $O/bench_pipe.json | cut -c 1-1500
-NX_FFT_PIPE=0 timeout 300 python bench.py --no-cpu-baseline --no-v1-shaped --steps 10 > $O/bench_old.json 2> $O/bench_old.err; tail -1 $O/bench_old.json | cut -c 1-600
+timeout 300 python bench.py --full --no-cpu-baseline --no-v1-shaped --steps 10 > $O/bench_pipe.json 2> $O/bench_pipe.err; tail -1 $O/bench_pipe.json | cut -c 1-1500
+NX_FFT_PIPE=0 timeout 300 python bench.py --full --no-cpu-baseline --no-v1-shaped --steps 10 > $O/bench_old.json 2> $O/bench_old.err; tail -1 $O/bench_old.json | cut -c 1-600

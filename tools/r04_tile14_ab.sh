@@ -14,7 +14,7 @@ for l in sys.stdin:
   done
 done
 for t in 0 1; do
-  NX_FFT_TILE14=$t python bench.py --log-rows 24 --steps 2 --warmup 1 --no-cpu-baseline --no-v1-shaped --no-host-trace | python -c "
+  NX_FFT_TILE14=$t python bench.py --full --log-rows 24 --steps 2 --warmup 1 --no-cpu-baseline --no-v1-shaped --no-host-trace | python -c "
 import sys, json
 r = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print(json.dumps({'tile14': $t, 'bench_log_rows': 24, 'ms_per_prove': r['ms_per_step'], 'cycles_per_s': r['value'], 'lde_kernel_ms': r['roofline']['kernel_ms'], 'lde_alg_GBs': r['roofline']['achieved'], 'frac': r['roofline']['frac'], 'stages_ms': r['stages_ms']}))" >> "$out"

@@ -5,13 +5,13 @@ O=${EV_OUT:-gpurun_out/r06/ev}; mkdir -p $O
 export TMPDIR=/tmp
 R=$PWD
 # 1. the driver's line (N = 1): headline + v1-shaped (+ the reference's tuple widths) + host trace + preprocessed reuse + cpu_baseline
-timeout 1200 python bench.py --steps 20 > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c 1-300
+timeout 1200 python bench.py --full --steps 20 > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c 1-300
 # 2. rocprofv3 kernel traces of the same command (headline) and of the v1-shaped statement; the kernel sequence / GPU idle gaps of one headline prove
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt_bench -o kt -- python bench.py --no-cpu-baseline --no-v1-shaped --no-host-trace --steps 5 > /dev/null 2>&1
-python tools/rocprof_summary.py $O/kt_bench/kt_results.db $O/bench_kernel_stats.txt "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-v1-shaped --no-host-trace --steps 5"
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt_bench -o kt -- python bench.py --full --no-cpu-baseline --no-v1-shaped --no-host-trace --steps 5 > /dev/null 2>&1
+python tools/rocprof_summary.py $O/kt_bench/kt_results.db $O/bench_kernel_stats.txt "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-v1-shaped --no-host-trace --steps 5"
 # (kernel sequences come from step 2b: bench.py ends with a statistics prove, whose stages end in synchronisations — not what a timed prove does)
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt_v1 -o kt -- python bench.py --lcd 2 --n-logup 250 --extra-comps 8 --no-cpu-baseline --no-v1-shaped --no-host-trace --steps 2 > /dev/null 2>&1
-python tools/rocprof_summary.py $O/kt_v1/kt_results.db $O/v1_shaped_kernel_stats.txt "rocprofv3 --kernel-trace --stats -- python bench.py --lcd 2 --n-logup 250 --extra-comps 8 --no-cpu-baseline --no-v1-shaped --no-host-trace --steps 2"
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt_v1 -o kt -- python bench.py --full --lcd 2 --n-logup 250 --extra-comps 8 --no-cpu-baseline --no-v1-shaped --no-host-trace --steps 2 > /dev/null 2>&1
+python tools/rocprof_summary.py $O/kt_v1/kt_results.db $O/v1_shaped_kernel_stats.txt "rocprofv3 --kernel-trace --stats -- python bench.py --full --lcd 2 --n-logup 250 --extra-comps 8 --no-cpu-baseline --no-v1-shaped --no-host-trace --steps 2"
 rm -rf $O/kt_bench $O/kt_v1
 # 2b. where the GPU idles inside a TIMED prove: kernel sequences of plain proves (no statistics call) of the headline, the v1 shape and config #5 at the reference's tuple widths
 for W in headline v1 keccakw; do
@@ -27,7 +27,7 @@ timeout 100 tools/ubench/mall_bw > $O/mall_bw.jsonl 2>/dev/null
 # 3. HBM-side traffic of the Circle-FFT LDE (separate --pmc passes)
 timeout 400 python tools/pmc_traffic.py --out $O/fft_traffic.json > /dev/null 2>&1
 # 4. the headline statement at other sizes
-for n in 16 18 20 22 24; do st=20; [ $n -ge 22 ] && st=5; timeout 300 python bench.py --log-rows $n --no-cpu-baseline --no-v1-shaped --no-host-trace --steps $st 2>/dev/null | tail -1 | python -c "
+for n in 16 18 20 22 24; do st=20; [ $n -ge 22 ] && st=5; timeout 300 python bench.py --full --log-rows $n --no-cpu-baseline --no-v1-shaped --no-host-trace --steps $st 2>/dev/null | tail -1 | python -c "
 import sys, json
 r = json.loads(sys.stdin.read())
 print(json.dumps({'log_rows': r['config']['log_n_rows'], 'ms_per_step': round(r['ms_per_step'], 3), 'cycles_per_s': r['value'], 'lde_ms': round(r['roofline']['kernel_ms'], 3), 'lde_alg_GBs': round(r['roofline']['achieved'], 1), 'stages_ms': r['stages_ms']}))" >> $O/bench_sizes.jsonl; done
