@@ -47,6 +47,14 @@ extern "C" {
 #define NX_FRI_ALPHA_PREV 0  /* fold circle columns with the previous layer's alpha (newer Stwo)    */
 #define NX_FRI_ALPHA_FIRST 1 /* fold all circle columns with the first alpha (older Stwo)           */
 
+/* Element kind of one host column of the narrow upload entry points (nx_upload_columns_narrow, nx_prover_tree_commit_host_narrow,
+ * nx_prove_machine_host_narrow).  The device columns are u32 words whatever the kind. */
+#define NX_COL_U32 0        /* uint32_t elements: what the u32 entry points take, handled exactly as they handle it         */
+#define NX_COL_U16 1        /* uint16_t elements: sent as they are, widened on the device                                   */
+#define NX_COL_U8 2         /* uint8_t elements: sent as they are, widened on the device                                    */
+#define NX_COL_U32_AS_U16 3 /* uint32_t elements, every value < 2^16: packed to 2 bytes on host threads, sent narrow        */
+#define NX_COL_U32_AS_U8 4  /* uint32_t elements, every value < 2^8: packed to 1 byte on host threads, sent narrow          */
+
 typedef struct nx_ctx nx_ctx;
 typedef struct nx_twiddles nx_twiddles;
 typedef struct nx_tree nx_tree;
@@ -74,7 +82,8 @@ int nx_ctx_set_hash_mode(nx_ctx* ctx, int mode);
  * above it), "commit.pipe_cols" (leaf hashing beside the LDE in
  * groups of this many columns; 0 = off), "fri.device_channel", "fri.tail" (0 = off, 1 = the FRI layers of <= 2^11 points in one launch,
  * 2..11 = from 2^that many points), "logup.scan_tiled", "logup.per_column", "logup.staged" (nx_logup_cols requests
- * every read of a group of 8 fractions before it uses the first value; 0 = reads where they are used).
+ * every read of a group of 8 fractions before it uses the first value; 0 = reads where they are used).  "host.pack_threads" (1..64; default
+ * min(16, hardware threads)): host threads that pack NX_COL_U32_AS_U16 / NX_COL_U32_AS_U8 columns of the narrow upload entry points.
  * Unknown names and out-of-range values are NX_ERR_ARG.
  * None of them changes a result: proofs, roots and transforms are bit-identical under every setting. */
 int nx_ctx_set_option(nx_ctx* ctx, const char* name, int64_t value);
@@ -126,6 +135,20 @@ int nx_upload_columns(nx_ctx* ctx, const uint32_t* const* h_cols, uint32_t n_col
  * context's copies out of it. */
 int nx_host_pin(nx_ctx* ctx, const void* h, size_t bytes);
 int nx_host_unpin(nx_ctx* ctx, const void* h);
+/* nx_upload_columns for a trace whose columns are byte or half-word limbs: nearly every main column of the reference is a byte limb stored
+ * as u32 (IntoBaseFields for u32, prover/src/trace/utils.rs:57-61, filled by TracesBuilder, trace_builder.rs:19-32), so the u32 form
+ * sends four bytes per byte over PCIe.  kinds[i] (NX_COL_*; NULL = all NX_COL_U32) says what h_cols[i] holds.  NX_COL_U16 / NX_COL_U8
+ * columns are pinned in place at their real byte length (2^log_size x 2 or 1 bytes; a range pinned with nx_host_pin is recognised by
+ * that length) or go through the bounce buffer when they cannot be pinned, are copied as they are and widened on the device — fused
+ * with R3's permutation when coset_order != 0.  NX_COL_U32_AS_U16 / NX_COL_U32_AS_U8 columns are never pinned: "host.pack_threads"
+ * threads pack them into a pinned staging ring of the context (allocated on first use, released by nx_ctx_trim / nx_ctx_destroy) while
+ * the previous chunk of 16 columns is on the bus.  A value that does not fit its declared width is refused, never truncated: NX_ERR_ARG,
+ * and nx_last_error names the kind, the value, the column (index into h_cols) and the row (index into that column) — the lowest
+ * column, then row, whatever the thread count; the chunk that holds it is never sent, the caller's arrays are never written and the
+ * context stays usable.  A call whose columns are all NX_COL_U32 is nx_upload_columns.  Blocking: the host columns are free on return.
+ * NX_ERR_ARG for NULL arguments, zero columns or an unknown kind. */
+int nx_upload_columns_narrow(nx_ctx* ctx, const void* const* h_cols, const uint8_t* kinds, uint32_t n_cols, uint32_t log_size,
+                             uint32_t* const* d_cols, int coset_order);
 
 /* ----------------------------------------------------- K2-K4, K7: PolyOps ------------------ */
 /* K2 — PolyOps::precompute_twiddles(CanonicCoset::new(log_half_coset + 1).half_coset())
@@ -363,6 +386,15 @@ int nx_prove_machine(nx_ctx* ctx, const nx_component_spec* comps, uint32_t n_com
 int nx_prove_machine_host(nx_ctx* ctx, const nx_component_spec* comps, uint32_t n_comps, const nx_pcs_config* cfg,
                           const uint32_t* const* h_pre_cols, const uint32_t* const* h_main_cols, int coset_order, const uint8_t* ad,
                           size_t ad_len, uint32_t** proof_words, size_t* n_words, nx_prove_stats* stats);
+/* nx_prove_machine_host with an element kind per host column (NX_COL_*; nx_upload_columns_narrow describes the kinds, the pinning and
+ * the refusal): pre_kinds[i] / main_kinds[i] for h_pre_cols[i] / h_main_cols[i], NULL = all NX_COL_U32.  The byte limbs of the
+ * reference's main trace (trace_builder.rs:19-32) cross PCIe as bytes.  A refused value fails the proof with NX_ERR_ARG naming the
+ * trace (preprocessed / main), the column index within that array and the row; nothing of the proof is returned and the context can
+ * prove again.  One GPU; blocking; the host columns are free on return.  The proof equals nx_prove_machine_host's for the same values. */
+int nx_prove_machine_host_narrow(nx_ctx* ctx, const nx_component_spec* comps, uint32_t n_comps, const nx_pcs_config* cfg,
+                                 const void* const* h_pre_cols, const uint8_t* pre_kinds, const void* const* h_main_cols,
+                                 const uint8_t* main_kinds, int coset_order, const uint8_t* ad, size_t ad_len, uint32_t** proof_words,
+                                 size_t* n_words, nx_prove_stats* stats);
 /* `Proof.claimed_sum` of the last successful nx_prove_machine on this context (reference prover/src/machine.rs:93-98: the proof the
  * reference returns carries the per-component logup claimed sums next to the StarkProof; a verifier mixes them before the interaction
  * commitment, machine.rs:262 / :448-450, and nx_proof_serialize_stwo takes them): 4 words per component, in component order.
@@ -569,6 +601,14 @@ int nx_prover_tree_commit(nx_prover* prover, uint8_t root[32]);
  * A row-sharded session uploads its own columns first (no overlap) and commits as usual. */
 int nx_prover_tree_commit_host(nx_prover* prover, const uint32_t* const* h_cols, int coset_order, const uint32_t* keep_idx,
                                uint32_t n_keep, uint32_t* const* d_keep, uint8_t root[32]);
+/* nx_prover_tree_commit_host with an element kind per host column (kinds[i] for h_cols[i], NX_COL_*; NULL = all NX_COL_U32): the
+ * reference's byte-limb trace columns (TracesBuilder, trace_builder.rs:19-32) cross PCIe as bytes and are widened on the device under
+ * the commit's transforms; nx_upload_columns_narrow describes the kinds, the pinning and the refusal.  A refused value returns NX_ERR_ARG
+ * before the root is mixed: the transcript is untouched, the tree is no longer begun, and the caller may nx_prover_tree_begin the same
+ * tree again and commit corrected columns — the proof is then the one that never saw the refusal.  Blocking; the host columns are free
+ * on return.  A row-sharded session uploads its own columns through nx_upload_columns_narrow first, as the u32 form does. */
+int nx_prover_tree_commit_host_narrow(nx_prover* prover, const void* const* h_cols, const uint8_t* kinds, int coset_order,
+                                      const uint32_t* keep_idx, uint32_t n_keep, uint32_t* const* d_keep, uint8_t root[32]);
 /* A committed tree that is proved over and over — the preprocessed tree: the reference commits the same preprocessed + program columns
  * in every proof of a program (prover/src/machine.rs:208-228) and once more in every verification (machine.rs:363-417, verify.rs:103-143,
  * which needs only the root) — need not be transformed and hashed again.  nx_prover_tree_share turns committed tree `tree_index` of a

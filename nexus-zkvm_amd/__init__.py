@@ -21,6 +21,8 @@ P = (1 << 31) - 1
 NX_OK = 0
 HASH_BLAKE2S, HASH_BLAKE2S_RAW0 = 0, 1
 FRI_ALPHA_PREV, FRI_ALPHA_FIRST = 0, 1
+# element kinds of the narrow host-column entry points (NX_COL_* of include/nexus_hip.h)
+COL_U32, COL_U16, COL_U8, COL_U32_AS_U16, COL_U32_AS_U8 = 0, 1, 2, 3, 4
 
 
 class LocalGroup:
@@ -343,6 +345,24 @@ class ProverSession:
                                                          kd if len(kept) else None, root.ctypes.data_as(C.c_void_p)))
         return root, kept
 
+    def commit_host_narrow(self, cols, coset_order=False, keep=(), as_kind=None):
+        """nx_prover_tree_commit_host_narrow: commit_host for host columns of uint8 / uint16 / uint32 arrays (the kind follows the dtype;
+        as_kind declares uint32 columns to hold byte or half-word values, see _narrow_columns).  Narrow columns cross PCIe narrow and are
+        widened on the device.  A value that does not fit its declared width raises; the tree is then no longer begun and the transcript
+        is untouched.  Returns (root, {index: DeviceColumns})."""
+        arrs, kinds = _narrow_columns(cols, as_kind)
+        logs = [int(np.log2(len(c))) for c in arrs]
+        self.tree_begin(logs)
+        hp = (C.c_void_p * max(1, len(arrs)))(*[c.ctypes.data for c in arrs])
+        kept = {int(k): DeviceColumns(self.be, 1, logs[int(k)]) for k in keep}
+        ki = _u32(list(kept.keys()))
+        kd = (C.c_void_p * max(1, len(kept)))(*[d.ptr.value for d in kept.values()])
+        root = np.zeros(8, np.uint32)
+        self.be._chk(self.be.L.nx_prover_tree_commit_host_narrow(self.h, hp, kinds.ctypes.data_as(C.c_void_p), int(bool(coset_order)),
+                                                                ki.ctypes.data_as(C.c_void_p) if len(kept) else None, len(kept),
+                                                                kd if len(kept) else None, root.ctypes.data_as(C.c_void_p)))
+        return root, kept
+
     def share_tree(self, tree_index):
         """nx_prover_tree_share: committed tree `tree_index` of this session as a handle other sessions of the same backend can adopt."""
         h = C.c_void_p()
@@ -473,6 +493,39 @@ def declared_symbols():
 
 def _u32(a):
     return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _as_width(spec):
+    """A narrower width for a uint32 column: np.uint8 / np.uint16 (or "u8" / "u16"); None keeps it uint32."""
+    if spec is None:
+        return None
+    name = spec if isinstance(spec, str) else np.dtype(spec).name
+    w = {"u8": 1, "uint8": 1, "u16": 2, "uint16": 2}.get(name)
+    if w is None:
+        raise ValueError(f"as_kind: {spec!r} is not a narrower width (uint8 / uint16)")
+    return w
+
+
+def _narrow_columns(cols, as_kind=None):
+    """Host columns of the narrow entry points -> (contiguous arrays to keep alive, their NX_COL_* kinds as a uint8 array).  The kind
+    follows the dtype (uint8 / uint16 / uint32); as_kind (one spec for every uint32 column, or one per column, None = as it is) declares a
+    uint32 column's values to fit 1 or 2 bytes: the library packs it on host threads and refuses a value that does not fit."""
+    cols = list(cols)
+    per = list(as_kind) if isinstance(as_kind, (list, tuple)) else [as_kind] * len(cols)
+    if len(per) != len(cols):
+        raise ValueError("as_kind: one entry per column")
+    arrs, kinds = [], []
+    for c, spec in zip(cols, per):
+        a = np.asarray(c)
+        if a.dtype in (np.uint8, np.uint16):
+            if spec is not None:
+                raise ValueError("as_kind applies to uint32 columns only")
+            arrs.append(np.ascontiguousarray(a)); kinds.append(COL_U8 if a.dtype == np.uint8 else COL_U16)
+            continue
+        arrs.append(_u32(a))
+        w = _as_width(spec)
+        kinds.append(COL_U32 if w is None else COL_U32_AS_U8 if w == 1 else COL_U32_AS_U16)
+    return arrs, np.array(kinds, dtype=np.uint8)
 
 
 def default_config(pow_bits=10, log_blowup=1, n_queries=3, log_last_layer_degree_bound=0, hash_mode=HASH_BLAKE2S,
@@ -684,6 +737,17 @@ class HipBackend:
         out = DeviceColumns(self, len(cols), log)
         hp = (C.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
         self._chk(self.L.nx_upload_columns(self.ctx, hp, len(cols), log, out.col_ptrs(), 1 if coset_order else 0))
+        return out
+
+    def upload_columns_narrow(self, host_cols, coset_order=True, as_kind=None):
+        """nx_upload_columns_narrow: upload_columns for host columns of uint8 / uint16 / uint32 arrays of one size (the kind follows the
+        dtype; as_kind declares uint32 columns to hold byte or half-word values).  Narrow columns cross PCIe narrow and are widened on
+        the device; a value that does not fit its declared width raises NexusHipError.  -> DeviceColumns of u32 words."""
+        arrs, kinds = _narrow_columns(host_cols, as_kind)
+        log = int(np.log2(arrs[0].size))
+        out = DeviceColumns(self, len(arrs), log)
+        hp = (C.c_void_p * len(arrs))(*[c.ctypes.data for c in arrs])
+        self._chk(self.L.nx_upload_columns_narrow(self.ctx, hp, kinds.ctypes.data_as(C.c_void_p), len(arrs), log, out.col_ptrs(), 1 if coset_order else 0))
         return out
 
     def host_pin(self, arr):
@@ -1056,6 +1120,25 @@ class HipBackend:
         adb = (C.c_uint8 * max(1, len(ad)))(*ad)
         self._chk(self.L.nx_prove_machine_host(self.ctx, self._comps(comps), len(comps), C.byref(cfg), pp, mp, int(bool(coset_order)), adb, C.c_size_t(len(ad)),
                                                C.byref(words), C.byref(n), C.byref(stats) if want_stats else None))
+        out = np.ctypeslib.as_array(words, shape=(n.value,)).copy()
+        self.L.nx_free_host(words)
+        return (out, stats.as_dict()) if want_stats else out
+
+    def prove_machine_host_narrow(self, comps, cfg, pre_cols, main_cols, ad=b"", coset_order=False, want_stats=False, pre_as=None, main_as=None):
+        """nx_prove_machine_host_narrow: prove_machine_host with host columns of uint8 / uint16 / uint32 arrays (the kind follows the
+        dtype; pre_as / main_as declare uint32 columns to hold byte or half-word values, as as_kind of upload_columns_narrow).  Same proof
+        as prove_machine_host for the same values; a value that does not fit its declared width raises NexusHipError."""
+        cfg = cfg or default_config()
+        pre, pk = _narrow_columns(pre_cols, pre_as)
+        main, mk = _narrow_columns(main_cols, main_as)
+        pp = (C.c_void_p * max(1, len(pre)))(*[c.ctypes.data for c in pre])
+        mp = (C.c_void_p * max(1, len(main)))(*[c.ctypes.data for c in main])
+        words, n = C.POINTER(C.c_uint32)(), C.c_size_t(0)
+        stats = ProveStats()
+        adb = (C.c_uint8 * max(1, len(ad)))(*ad)
+        self._chk(self.L.nx_prove_machine_host_narrow(self.ctx, self._comps(comps), len(comps), C.byref(cfg), pp, pk.ctypes.data_as(C.c_void_p), mp,
+                                                      mk.ctypes.data_as(C.c_void_p), int(bool(coset_order)), adb, C.c_size_t(len(ad)),
+                                                      C.byref(words), C.byref(n), C.byref(stats) if want_stats else None))
         out = np.ctypeslib.as_array(words, shape=(n.value,)).copy()
         self.L.nx_free_host(words)
         return (out, stats.as_dict()) if want_stats else out

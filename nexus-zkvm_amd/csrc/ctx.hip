@@ -6,6 +6,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <thread>
 
 namespace nx {
 
@@ -329,6 +330,7 @@ static nx_options options_from_env() {
     o.machine_reuse_pre = env_int("NX_MACHINE_REUSE_PREPROCESSED", 0) != 0;
     o.machine_logup_program = env_int("NX_MACHINE_LOGUP_PROGRAM", 0) != 0;
     o.machine_queue_trees = env_int("NX_MACHINE_QUEUE_TREES", 0) != 0;   // measured: no gain (profiles/r05_queue_trees_ab.txt)
+    o.host_pack_threads = clampi((int)std::thread::hardware_concurrency(), 1, 16);   // a GPU box grants a command 16 CPUs
     return o;
 }
 struct OptEntry { const char* name; int nx_options::*field; int lo, hi; };
@@ -358,6 +360,7 @@ static const OptEntry k_options[] = {
     {"machine.reuse_preprocessed", &nx_options::machine_reuse_pre, 0, 1},
     {"machine.queue_trees", &nx_options::machine_queue_trees, 0, 1},
     {"machine.logup_program", &nx_options::machine_logup_program, 0, 1},
+    {"host.pack_threads", &nx_options::host_pack_threads, 1, 64},
 };
 int nx_ctx_set_option(nx_ctx* ctx, const char* name, int64_t value) {
     if (!ctx || !name) return set_err(ctx, NX_ERR_ARG, "nx_ctx_set_option: NULL argument");
@@ -436,6 +439,7 @@ void nx_ctx_destroy(nx_ctx* ctx) {
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->h_scratch) (void)hipHostFree(ctx->h_scratch);
     if (ctx->h_bounce) { (void)hipHostFree(ctx->h_bounce); for (int k = 0; k < 2; k++) (void)hipEventDestroy(ctx->bounce_ev[k]); }
+    pack_ring_release(ctx);
     for (auto& kv : ctx->free_pinned) (void)hipHostFree(kv.second);
     for (auto& kv : ctx->live_pinned) (void)hipHostFree(kv.first);
     for (int i = 0; i < 3; i++) { (void)hipStreamDestroy(ctx->side[i]); (void)hipEventDestroy(ctx->join_ev[i]); }
@@ -454,7 +458,7 @@ int nx_ctx_set_hash_mode(nx_ctx* ctx, int mode) {
 }
 
 int nx_sync(nx_ctx* ctx) { NX_GUARD(ctx); if (!ctx) return set_err(nullptr, NX_ERR_ARG, "nx_sync: NULL context"); NX_HIP(ctx, hipStreamSynchronize(ctx->stream)); NX_HIP(ctx, hipStreamSynchronize(ctx->hash_stream)); return NX_OK; }
-int nx_ctx_trim(nx_ctx* ctx) { NX_GUARD(ctx); if (!ctx) return set_err(nullptr, NX_ERR_ARG, "nx_ctx_trim: NULL context"); NX_TRY(nx_sync(ctx)); dev_cache_release(ctx); return NX_OK; }
+int nx_ctx_trim(nx_ctx* ctx) { NX_GUARD(ctx); if (!ctx) return set_err(nullptr, NX_ERR_ARG, "nx_ctx_trim: NULL context"); NX_TRY(nx_sync(ctx)); dev_cache_release(ctx); pack_ring_release(ctx); return NX_OK; }
 void* nx_ctx_stream(nx_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
 int nx_alloc(nx_ctx* ctx, size_t n_words, uint32_t** d_out) {

@@ -17,6 +17,7 @@
 //  * The zero-extension of the LDE ("extend") is folded into the first evaluate pass: source words
 //    at index >= 2^log_in read as zero, nothing is materialised.
 #include "internal.h"
+#include "host/narrow_pack.h"
 #include <mutex>
 #include <atomic>
 #include <stdlib.h>
@@ -447,6 +448,28 @@ __global__ void finalize_kernel(ColSet src, ColSet dst, u32 n_cols, int log) {
     dst.col(c)[i] = src.col(c)[natural_index_of(i, log)];
 }
 
+// A narrow host column (NX_COL_U8 / NX_COL_U16 and the packed NX_COL_U32_AS_*: W bytes per value) widened to u32 words on the device.
+// PERMUTE (coset_order): R3's gather of finalize_kernel, reading W-byte values.  Else the loads are contiguous: one dwordx4 per lane,
+// 16 / W values, written as 16 / W / 4 dwordx4 stores (vec: the column holds >= 16 bytes and dst is 16-byte aligned); otherwise one value
+// per lane — the tail path of the columns smaller than one vector load.
+template <int W, bool PERMUTE>
+__global__ void __launch_bounds__(256) widen_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ dst, int log, int vec) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x, n = 1u << log;
+    auto at = [&](u32 j) -> u32 { return W == 1 ? (u32)src[j] : (u32)((const uint16_t*)src)[j]; };
+    if (PERMUTE) { if (i < n) dst[i] = at(natural_index_of(i, log)); return; }
+    constexpr u32 E = 16 / W;
+    if (!vec) { if (i < n) dst[i] = at(i); return; }
+    if (i >= n / E) return;
+    const uint4 v = gld4((const uint32_t*)(src + (size_t)i * 16));
+    uint32_t* d = dst + (size_t)i * E;
+    const u32 w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        if (W == 1) gst4(d + 4 * q, make_uint4(w[q] & 0xffu, (w[q] >> 8) & 0xffu, (w[q] >> 16) & 0xffu, w[q] >> 24));
+        else if (q < 2) gst4(d + 4 * q, make_uint4(w[2 * q] & 0xffffu, w[2 * q] >> 16, w[2 * q + 1] & 0xffffu, w[2 * q + 1] >> 16));
+    }
+}
+
 __global__ void twiddle_double_kernel(const u32* tw, const u32* itw, u32* tw2, u32* itw2, u32 n) {
     u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { tw2[i] = tw[i] << 1; itw2[i] = itw[i] << 1; }
@@ -636,7 +659,7 @@ int nx_upload_columns(nx_ctx* ctx, const uint32_t* const* h_cols, uint32_t n_col
 }  // extern "C" (re-opened below)
 namespace nx {
 int HostFeed::begin(nx_ctx* c, uint32_t log_size, int coset) {
-    ctx = c; log = log_size; coset_order = coset; n_done = 0;
+    ctx = c; log = log_size; coset_order = coset; n_done = n_slot = n_packed = 0;
     if (log_size < 1 || log_size > 30) return set_err(c, NX_ERR_ARG, "host feed: bad log_size");
     for (int k = 0; k < 2; k++) {
         if (coset_order) NX_TRY(dev_alloc(ctx, (size_t)4 << log, (void**)&d_tmp[k]));
@@ -653,53 +676,175 @@ int HostFeed::begin(nx_ctx* c, uint32_t log_size, int coset) {
     NX_HIP(ctx, hipStreamWaitEvent(ctx->perm_stream, here, 0));
     return NX_OK;
 }
-int HostFeed::chunk(const uint32_t* const* h_cols, uint32_t* const* d_cols, uint32_t n_cols, hipEvent_t* ready) {
+static int kind_width(uint8_t kind) { return kind == NX_COL_U8 || kind == NX_COL_U32_AS_U8 ? 1 : kind == NX_COL_U16 || kind == NX_COL_U32_AS_U16 ? 2 : 4; }
+static const char* kind_name(uint8_t kind) {
+    static const char* const names[] = {"NX_COL_U32", "NX_COL_U16", "NX_COL_U8", "NX_COL_U32_AS_U16", "NX_COL_U32_AS_U8"};
+    return kind <= NX_COL_U32_AS_U8 ? names[kind] : "an unknown kind";
+}
+// The staging ring of the packed columns holds at least `bytes` per slot (slots only grow; an old slot is freed once its copies are done).
+static int pack_ring_reserve(nx_ctx* ctx, size_t bytes) {
+    if (ctx->pack_bytes >= bytes) return NX_OK;
+    pack_ring_release(ctx);
+    for (int s = 0; s < 2; s++) {
+        NX_HIP(ctx, hipEventCreateWithFlags(&ctx->pack_ev[s], hipEventDisableTiming));
+        NX_HIP(ctx, hipEventRecord(ctx->pack_ev[s], ctx->copy_stream));           // a fresh slot: nothing reads it
+        if (hipHostMalloc((void**)&ctx->h_pack[s], bytes, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); pack_ring_release(ctx);
+            return set_err(ctx, NX_ERR_OOM, "host feed: pinned staging ring of the narrow upload");
+        }
+    }
+    ctx->pack_bytes = bytes;
+    return NX_OK;
+}
+void pack_ring_release(nx_ctx* ctx) {
+    for (int s = 0; s < 2; s++) {
+        if (ctx->pack_ev[s]) { (void)hipEventSynchronize(ctx->pack_ev[s]); (void)hipEventDestroy(ctx->pack_ev[s]); ctx->pack_ev[s] = nullptr; }
+        if (ctx->h_pack[s]) { (void)hipHostFree(ctx->h_pack[s]); ctx->h_pack[s] = nullptr; }
+    }
+    ctx->pack_bytes = 0;
+}
+int HostFeed::chunk(const void* const* h_cols, const uint8_t* kinds, const uint32_t* call_col, const char* what, uint32_t* const* d_cols, uint32_t n_cols,
+                    hipEvent_t* ready) {
     const size_t n = (size_t)1 << log, bytes = n * 4;
+    auto kind_of = [&](uint32_t c) -> uint8_t { return kinds ? kinds[c] : (uint8_t)NX_COL_U32; };
+    // 1. the chunk's NX_COL_U32_AS_* columns are packed and checked on host threads into a slot of the staging ring — before any copy
+    //    of the chunk is queued, so a refused chunk is never sent.  The slot's previous copies (two chunks ago) must be done.
+    std::vector<const uint8_t*> narrow_src(n_cols, nullptr);
+    int slot = -1;
+    {
+        std::vector<const uint32_t*> ps; std::vector<uint8_t*> pd; std::vector<uint8_t> pw; std::vector<uint32_t> pc;
+        size_t need = 0; int wmax = 0;
+        for (uint32_t c = 0; c < n_cols; c++) {
+            if (kind_of(c) > NX_COL_U32_AS_U8) return set_err(ctx, NX_ERR_ARG, "host feed: unknown column kind");
+            if (kind_of(c) >= NX_COL_U32_AS_U16) { const int w = kind_width(kind_of(c)); need += n * w; wmax = std::max(wmax, w); }
+        }
+        if (need) {
+            NX_TRY(pack_ring_reserve(ctx, std::max(need, (size_t)16 * n * wmax)));
+            slot = (int)(n_packed & 1);
+            NX_HIP(ctx, hipEventSynchronize(ctx->pack_ev[slot]));
+            size_t off = 0;
+            for (uint32_t c = 0; c < n_cols; c++) {
+                if (kind_of(c) < NX_COL_U32_AS_U16) continue;
+                if (!h_cols[c] || !d_cols[c]) return set_err(ctx, NX_ERR_ARG, "host feed: NULL column");
+                const int w = kind_width(kind_of(c));
+                ps.push_back((const uint32_t*)h_cols[c]); pd.push_back(ctx->h_pack[slot] + off); pw.push_back((uint8_t)w); pc.push_back(c);
+                narrow_src[c] = ctx->h_pack[slot] + off;
+                off += n * w;
+            }
+            PackViolation bad;
+            if (!pack_narrow(ps.data(), pd.data(), pw.data(), (uint32_t)ps.size(), n, ctx->opt.host_pack_threads, &bad)) {
+                const uint32_t c = pc[bad.col];
+                char msg[320];
+                snprintf(msg, sizeof msg, "%s column %u, row %llu: value %u does not fit %s (at most %u); refused, not truncated — nothing of its chunk was sent",
+                         what ? what : "host", call_col ? call_col[c] : c, (unsigned long long)bad.row, bad.value, kind_name(kind_of(c)), pw[bad.col] == 1 ? 255u : 65535u);
+                return set_err(ctx, NX_ERR_ARG, msg);
+            }
+            n_packed++;
+        }
+    }
+    // 2. the copies (and, for narrow columns, the widening behind them)
+    bool any_narrow = false;
     for (uint32_t c = 0; c < n_cols; c++) {
         if (!h_cols[c] || !d_cols[c]) return set_err(ctx, NX_ERR_ARG, "host feed: NULL column");
-        bool dma_ok = true;
-        if (host_pinned_by_owner(h_cols[c], bytes)) {}                      // pinned once by its owner (nx_host_pin)
-        else if (hipHostRegister((void*)h_cols[c], bytes, hipHostRegisterDefault) == hipSuccess) pinned.push_back(h_cols[c]);
-        else { (void)hipGetLastError(); dma_ok = false; }                         // not pinnable: through the bounce buffer (never a pin-in-place copy: internal.h, h_bounce)
-        const int k = (int)(n_done & 1);
-        auto h2d = [&](uint32_t* dst, hipStream_t st) -> int {
-            if (dma_ok) { NX_HIP(ctx, hipMemcpyAsync(dst, h_cols[c], bytes, hipMemcpyHostToDevice, st)); return NX_OK; }
-            return copy_h2d_blocking(ctx, dst, h_cols[c], bytes, st);
-        };
-        if (!coset_order) {
-            // no permutation to run: the second stream carries every other column's copy (two DMA queues in flight: 136.6 -> 132.7 ms
-            // for the 374-column headline trace, bench.py host_trace)
-            NX_TRY(h2d(d_cols[c], (n_done & 1) ? ctx->perm_stream : ctx->copy_stream));
-        } else {
-            if (n_done >= 2) NX_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, consumed[k], 0));      // the permutation of column n_done - 2 has read d_tmp[k]
-            NX_TRY(h2d(d_tmp[k], ctx->copy_stream));
-            NX_HIP(ctx, hipEventRecord(copied[k], ctx->copy_stream));
-            NX_HIP(ctx, hipStreamWaitEvent(ctx->perm_stream, copied[k], 0));
-            ColSet s1, d1; s1.base = d_tmp[k]; s1.stride = 0; s1.table = nullptr; d1.base = d_cols[c]; d1.stride = 0; d1.table = nullptr;
-            hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + 255) / 256), 1), dim3(256), 0, ctx->perm_stream, s1, d1, 1u, (int)log);
-            NX_LAUNCH_CHECK(ctx);
-            NX_HIP(ctx, hipEventRecord(consumed[k], ctx->perm_stream));
+        const uint8_t kind = kind_of(c);
+        if (kind == NX_COL_U32) {
+            const uint32_t* h = (const uint32_t*)h_cols[c];
+            bool dma_ok = true;
+            if (host_pinned_by_owner(h, bytes)) {}                      // pinned once by its owner (nx_host_pin)
+            else if (hipHostRegister((void*)h, bytes, hipHostRegisterDefault) == hipSuccess) pinned.push_back(h);
+            else { (void)hipGetLastError(); dma_ok = false; }                         // not pinnable: through the bounce buffer (never a pin-in-place copy: internal.h, h_bounce)
+            const int k = (int)(n_slot & 1);
+            auto h2d = [&](uint32_t* dst, hipStream_t st) -> int {
+                if (dma_ok) { NX_HIP(ctx, hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, st)); return NX_OK; }
+                return copy_h2d_blocking(ctx, dst, h, bytes, st);
+            };
+            if (!coset_order) {
+                // no permutation to run: the second stream carries every other column's copy (two DMA queues in flight: 136.6 -> 132.7 ms
+                // for the 374-column headline trace, bench.py host_trace)
+                NX_TRY(h2d(d_cols[c], (n_done & 1) ? ctx->perm_stream : ctx->copy_stream));
+            } else {
+                if (n_slot >= 2) NX_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, consumed[k], 0));      // the permutation of column n_slot - 2 has read d_tmp[k]
+                NX_TRY(h2d(d_tmp[k], ctx->copy_stream));
+                NX_HIP(ctx, hipEventRecord(copied[k], ctx->copy_stream));
+                NX_HIP(ctx, hipStreamWaitEvent(ctx->perm_stream, copied[k], 0));
+                ColSet s1, d1; s1.base = d_tmp[k]; s1.stride = 0; s1.table = nullptr; d1.base = d_cols[c]; d1.stride = 0; d1.table = nullptr;
+                hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + 255) / 256), 1), dim3(256), 0, ctx->perm_stream, s1, d1, 1u, (int)log);
+                NX_LAUNCH_CHECK(ctx);
+                NX_HIP(ctx, hipEventRecord(consumed[k], ctx->perm_stream));
+                n_slot++;
+            }
+            n_done++;
+            continue;
         }
+        // a narrow column: its W-byte values into a d_tmp slot and widened into d_cols[c], both on one of the two queues (alternating with the
+        // slot, as the u32 !coset_order copies alternate: two DMA queues in flight)
+        any_narrow = true;
+        const int w = kind_width(kind);
+        const size_t nb = n * w;
+        const void* src = narrow_src[c];
+        bool dma_ok = true;
+        if (!src) {
+            src = h_cols[c];
+            if (host_pinned_by_owner(src, nb)) {}
+            else if (hipHostRegister((void*)src, nb, hipHostRegisterDefault) == hipSuccess) pinned.push_back(src);
+            else { (void)hipGetLastError(); dma_ok = false; }
+        }
+        const int k = (int)(n_slot & 1);
+        hipStream_t st = k ? ctx->perm_stream : ctx->copy_stream;
+        if (!d_tmp[k]) {
+            // !coset_order allocates its slots on the first narrow column: like begin(), the feed's streams start behind the frees queued so far
+            NX_TRY(dev_alloc(ctx, bytes, (void**)&d_tmp[k]));
+            hipEvent_t here = nullptr;
+            NX_HIP(ctx, hipEventCreateWithFlags(&here, hipEventDisableTiming));
+            events.push_back(here);
+            NX_HIP(ctx, hipEventRecord(here, ctx->stream));
+            NX_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, here, 0));
+            NX_HIP(ctx, hipStreamWaitEvent(ctx->perm_stream, here, 0));
+        }
+        if (n_slot >= 2) NX_HIP(ctx, hipStreamWaitEvent(st, consumed[k], 0));      // the column of slot k before this one has been read
+        if (dma_ok) NX_HIP(ctx, hipMemcpyAsync(d_tmp[k], src, nb, hipMemcpyHostToDevice, st));
+        else NX_TRY(copy_h2d_blocking(ctx, d_tmp[k], src, nb, st));
+        const uint8_t* s8 = (const uint8_t*)d_tmp[k];
+        // every runtime call above was checked by its return code; the launch check below must see this launch's status only (the pin
+        // attempts of narrow columns leave a stale "not registered" status behind them: HIP error 713 on MI355X)
+        (void)hipGetLastError();
+        if (coset_order) {
+            const dim3 grid((unsigned)((n + 255) / 256));
+            if (w == 1) hipLaunchKernelGGL((widen_kernel<1, true>), grid, dim3(256), 0, st, s8, d_cols[c], (int)log, 0);
+            else hipLaunchKernelGGL((widen_kernel<2, true>), grid, dim3(256), 0, st, s8, d_cols[c], (int)log, 0);
+        } else {
+            const size_t per_lane = (size_t)(16 / w);
+            const int vec = n >= per_lane && !((uintptr_t)d_cols[c] & 15);
+            const size_t lanes = vec ? n / per_lane : n;
+            const dim3 grid((unsigned)((lanes + 255) / 256));
+            if (w == 1) hipLaunchKernelGGL((widen_kernel<1, false>), grid, dim3(256), 0, st, s8, d_cols[c], (int)log, vec);
+            else hipLaunchKernelGGL((widen_kernel<2, false>), grid, dim3(256), 0, st, s8, d_cols[c], (int)log, vec);
+        }
+        NX_LAUNCH_CHECK(ctx);
+        NX_HIP(ctx, hipEventRecord(consumed[k], st));
+        n_slot++;
         n_done++;
     }
     hipEvent_t ev = nullptr;
     NX_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     events.push_back(ev);
-    if (!coset_order) {                                     // the chunk is ready when both queues are through it
+    const bool join = !coset_order || any_narrow;
+    if (join) {                                             // the chunk is ready when both queues are through it
         hipEvent_t evp = nullptr;
         NX_HIP(ctx, hipEventCreateWithFlags(&evp, hipEventDisableTiming));
         events.push_back(evp);
         NX_HIP(ctx, hipEventRecord(evp, ctx->perm_stream));
         NX_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, evp, 0));
     }
-    NX_HIP(ctx, hipEventRecord(ev, coset_order ? ctx->perm_stream : ctx->copy_stream));
+    if (slot >= 0) NX_HIP(ctx, hipEventRecord(ctx->pack_ev[slot], ctx->copy_stream));     // after the join: the slot is free once both queues have read it
+    NX_HIP(ctx, hipEventRecord(ev, join ? ctx->copy_stream : ctx->perm_stream));
     *ready = ev;
     return NX_OK;
 }
 int HostFeed::finish() {
     if (!ctx) return NX_OK;
     hipError_t e1 = hipStreamSynchronize(ctx->copy_stream), e2 = hipStreamSynchronize(ctx->perm_stream);
-    for (const uint32_t* h : pinned) (void)hipHostUnregister((void*)h);
+    for (const void* h : pinned) (void)hipHostUnregister((void*)h);
     pinned.clear();
     for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
     events.clear();
@@ -760,6 +905,38 @@ int nx_host_unpin(nx_ctx* ctx, const void* h) {
     NX_HIP(ctx, hipHostUnregister((void*)h));
     return NX_OK;
 }
+
+int nx_upload_columns_narrow(nx_ctx* ctx, const void* const* h_cols, const uint8_t* kinds, uint32_t n_cols, uint32_t log_size, uint32_t* const* d_cols,
+                             int coset_order) {
+    NX_GUARD(ctx);
+    if (!ctx || !h_cols || !d_cols || !n_cols) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns_narrow: NULL argument or no columns");
+    std::vector<uint32_t> idx(n_cols);
+    for (uint32_t c = 0; c < n_cols; c++) idx[c] = c;
+    return upload_columns_narrow(ctx, h_cols, kinds, n_cols, log_size, d_cols, coset_order, idx.data(), "nx_upload_columns_narrow: h_cols");
+}
+
+}  // extern "C" (re-opened below)
+namespace nx {
+int upload_columns_narrow(nx_ctx* ctx, const void* const* h_cols, const uint8_t* kinds, uint32_t n_cols, uint32_t log_size, uint32_t* const* d_cols,
+                          int coset_order, const uint32_t* call_col, const char* what) {
+    bool any_narrow = false;
+    for (uint32_t c = 0; c < n_cols && kinds; c++) {
+        if (kinds[c] > NX_COL_U32_AS_U8) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns_narrow: unknown column kind");
+        any_narrow |= kinds[c] != NX_COL_U32;
+    }
+    if (!any_narrow) return nx_upload_columns(ctx, (const uint32_t* const*)h_cols, n_cols, log_size, d_cols, coset_order);
+    if (log_size < 1 || log_size > 30) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns_narrow: bad log_size");
+    for (uint32_t c = 0; c < n_cols; c++) if (!h_cols[c] || !d_cols[c]) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns_narrow: NULL column");
+    HostFeed feed;                                           // finish() on every path: the host columns are the caller's again on return
+    NX_TRY(feed.begin(ctx, log_size, coset_order));
+    for (uint32_t c0 = 0; c0 < n_cols; c0 += 16) {           // 16-column chunks: the pack of one runs while the previous one is on the bus
+        hipEvent_t ready = nullptr;
+        NX_TRY(feed.chunk(h_cols + c0, kinds + c0, call_col + c0, what, d_cols + c0, std::min(16u, n_cols - c0), &ready));
+    }
+    return feed.finish();
+}
+}  // namespace nx
+extern "C" {
 
 int nx_upload_coset_order(nx_ctx* ctx, const uint32_t* h_natural, uint32_t log_size, uint32_t* d_dst) {
     NX_GUARD(ctx);

@@ -39,6 +39,7 @@ struct nx_options {
     int machine_queue_trees;      // "machine.queue_trees": nx_prove_machine queues the preprocessed and the main tree builds before fetching the first root (1) or commits them one after the other (0; A/B)
     int machine_reuse_pre;        // "machine.reuse_preprocessed": nx_prove_machine keeps the committed preprocessed tree of a statement shape in the context and adopts it in later proofs (nx_prover_tree_adopt's rule; default 0: every proof commits it afresh, as the reference does)
     int air_degree_split;         // "air.degree_split": constraints of degree <= 3 of a component with a bound > 1 are evaluated on the log_size + 1 domain
+    int host_pack_threads;        // "host.pack_threads": host threads that pack NX_COL_U32_AS_* columns (HostFeed)
 };
 
 struct nx_ctx {
@@ -66,6 +67,10 @@ struct nx_ctx {
     // the mapping down under the next copy: "Memory access fault by GPU ... on address <host heap>" (reproduced 1 run in 4, round 5).
     // Through the bounce buffer no caller page is ever pinned implicitly.
     uint8_t* h_bounce = nullptr; hipEvent_t bounce_ev[2] = {nullptr, nullptr};
+    // Pinned staging ring of the narrow upload (HostFeed, NX_COL_U32_AS_*): two slots of one 16-column chunk at 1 or 2 bytes per value,
+    // allocated on first use (pinning hundreds of MiB per proof would cost milliseconds) and released by nx_ctx_trim / nx_ctx_destroy.
+    // pack_ev[s]: recorded on copy_stream after the copies that read slot s; the host waits on it before it packs into the slot again.
+    uint8_t* h_pack[2] = {nullptr, nullptr}; size_t pack_bytes = 0; hipEvent_t pack_ev[2] = {nullptr, nullptr};
     // caching allocator: freed device blocks are kept by exact size and handed back to later nx_alloc calls
     // (a prove repeats the same slab sizes); reuse is safe because all work is ordered on ctx->stream.
     std::multimap<size_t, void*> free_blocks;
@@ -226,13 +231,23 @@ int copy_h2d_blocking(nx_ctx* ctx, void* d_dst, const void* h_src, size_t bytes,
 int copy_d2h_blocking(nx_ctx* ctx, void* h_dst, const void* d_src, size_t bytes);
 // stream-ordered upload of caller host memory that may be freed as soon as this returns (through the staging ring, in chunks)
 int upload_async_staged(nx_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
+// Narrow columns (kinds != null, NX_COL_* of include/nexus_hip.h): an NX_COL_U16 / NX_COL_U8 column is pinned at its real byte length,
+// copied into a d_tmp slot and widened by widen_kernel on perm_stream; an NX_COL_U32_AS_* column is packed (and checked) on host
+// threads into the context's staging ring first (h_pack), then copied and widened the same way.  The chunk's packing ends before any of
+// its copies is queued, so a refused chunk is never sent.  call_col: index of each column in the caller's array (the refusal names it);
+// what: the caller's name of that array.  An NX_COL_U32 column takes the u32 path unchanged.
+void pack_ring_release(nx_ctx* ctx);
+// nx_upload_columns_narrow with the caller's column indices (call_col) and array name (what) for the refusal's message
+int upload_columns_narrow(nx_ctx* ctx, const void* const* h_cols, const uint8_t* kinds, uint32_t n_cols, uint32_t log_size, uint32_t* const* d_cols,
+                          int coset_order, const uint32_t* call_col, const char* what);
 struct HostFeed {
     nx_ctx* ctx = nullptr; int coset_order = 0; uint32_t log = 0;
     uint32_t* d_tmp[2] = {nullptr, nullptr}; hipEvent_t copied[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
-    uint64_t n_done = 0;
-    std::vector<const uint32_t*> pinned; std::vector<hipEvent_t> events;
+    uint64_t n_done = 0, n_slot = 0, n_packed = 0;      // columns fed / through a d_tmp slot / chunks packed into the staging ring
+    std::vector<const void*> pinned; std::vector<hipEvent_t> events;
     int begin(nx_ctx* c, uint32_t log_size, int coset);
-    int chunk(const uint32_t* const* h_cols, uint32_t* const* d_cols, uint32_t n_cols, hipEvent_t* ready);
+    int chunk(const uint32_t* const* h_cols, uint32_t* const* d_cols, uint32_t n_cols, hipEvent_t* ready) { return chunk((const void* const*)h_cols, nullptr, nullptr, nullptr, d_cols, n_cols, ready); }
+    int chunk(const void* const* h_cols, const uint8_t* kinds, const uint32_t* call_col, const char* what, uint32_t* const* d_cols, uint32_t n_cols, hipEvent_t* ready);
     int finish();
     ~HostFeed() { (void)finish(); }
 };

@@ -586,7 +586,11 @@ static std::set<uint32_t> logup_needed_columns(const nx_component_spec& c, uint3
 
 // host: the preprocessed and the main trace handed over in HOST memory (component after component, column after column; NULL = generate
 // them on the device from `seed`): the commits then upload them chunk by chunk under their own transforms (TreeBuilder::extend_evals_host)
-struct HostTrace { const uint32_t* const* pre = nullptr; const uint32_t* const* main = nullptr; int coset_order = 0; };
+// pre_kinds / main_kinds: the element kind of every host column (NX_COL_*, nx_prove_machine_host_narrow), null = all NX_COL_U32
+struct HostTrace {
+    const void* const* pre = nullptr; const void* const* main = nullptr; int coset_order = 0;
+    const uint8_t* pre_kinds = nullptr; const uint8_t* main_kinds = nullptr;
+};
 static int prove_machine(nx_ctx* ctx, const nx_component_spec* comps, uint32_t n_comps, const nx_pcs_config* ucfg, uint64_t seed, const uint8_t* ad,
                          size_t ad_len, const nx_comm* comm, std::vector<uint32_t>* words, nx_prove_stats* st, const HostTrace* host = nullptr) {
     PcsConfig cfg = {ucfg->pow_bits, ucfg->log_blowup, ucfg->n_queries, ucfg->log_last_layer_degree_bound, ucfg->fri_alpha_mode, ucfg->log_constraint_degree};
@@ -658,7 +662,11 @@ static int prove_machine(nx_ctx* ctx, const nx_component_spec* comps, uint32_t n
                     size_t q = 0;
                     for (uint32_t k : need) { uint32_t* dst = kb.p + (q++ << log); keep.push_back({k, dst}); kp[k] = dst; }
                 }
-                tb.extend_evals_host(std::move(slab), n_tree, log, (tree == 0 ? host->pre + locs[i].pre0 : host->main + locs[i].main0), host->coset_order, keep);
+                const uint32_t col0 = tree == 0 ? locs[i].pre0 : locs[i].main0;
+                const uint8_t* kinds = tree == 0 ? host->pre_kinds : host->main_kinds;
+                if (kinds) tb.extend_evals_host(std::move(slab), n_tree, log, (tree == 0 ? host->pre : host->main) + col0, kinds + col0, host->coset_order, keep, col0,
+                                                tree == 0 ? "nx_prove_machine_host_narrow: h_pre_cols (preprocessed trace)" : "nx_prove_machine_host_narrow: h_main_cols (main trace)");
+                else tb.extend_evals_host(std::move(slab), n_tree, log, (const uint32_t* const*)(tree == 0 ? host->pre : host->main) + col0, host->coset_order, keep);
                 continue;
             }
             if (!need.empty()) {
@@ -901,9 +909,24 @@ int nx_prove_machine_host(nx_ctx* ctx, const nx_component_spec* comps, uint32_t 
                           nx_prove_stats* stats) {
     NX_GUARD(ctx);
     if (!ctx || !comps || !cfg || !proof_words || !n_words || !h_pre_cols || !h_main_cols) return set_err(ctx, NX_ERR_ARG, "nx_prove_machine_host: NULL argument");
-    nxhip::HostTrace host; host.pre = h_pre_cols; host.main = h_main_cols; host.coset_order = coset_order;
+    nxhip::HostTrace host; host.pre = (const void* const*)h_pre_cols; host.main = (const void* const*)h_main_cols; host.coset_order = coset_order;
     std::vector<uint32_t> w;
     return hand_out(ctx, nxhip::prove_machine(ctx, comps, n_comps, cfg, 0, ad, ad_len, nullptr, &w, stats, &host), w, proof_words, n_words, "nx_prove_machine_host");
+}
+
+int nx_prove_machine_host_narrow(nx_ctx* ctx, const nx_component_spec* comps, uint32_t n_comps, const nx_pcs_config* cfg, const void* const* h_pre_cols,
+                                 const uint8_t* pre_kinds, const void* const* h_main_cols, const uint8_t* main_kinds, int coset_order, const uint8_t* ad,
+                                 size_t ad_len, uint32_t** proof_words, size_t* n_words, nx_prove_stats* stats) {
+    NX_GUARD(ctx);
+    if (!ctx || !comps || !n_comps || !cfg || !proof_words || !n_words || !h_pre_cols || !h_main_cols)
+        return set_err(ctx, NX_ERR_ARG, "nx_prove_machine_host_narrow: NULL argument");
+    size_t n_pre = 0, n_main = 0;
+    for (uint32_t i = 0; i < n_comps; i++) { n_pre += comps[i].n_pre; n_main += comps[i].n_main; }
+    for (size_t k = 0; k < n_pre && pre_kinds; k++) if (pre_kinds[k] > NX_COL_U32_AS_U8) return set_err(ctx, NX_ERR_ARG, "nx_prove_machine_host_narrow: unknown kind in pre_kinds");
+    for (size_t k = 0; k < n_main && main_kinds; k++) if (main_kinds[k] > NX_COL_U32_AS_U8) return set_err(ctx, NX_ERR_ARG, "nx_prove_machine_host_narrow: unknown kind in main_kinds");
+    nxhip::HostTrace host; host.pre = h_pre_cols; host.main = h_main_cols; host.coset_order = coset_order; host.pre_kinds = pre_kinds; host.main_kinds = main_kinds;
+    std::vector<uint32_t> w;
+    return hand_out(ctx, nxhip::prove_machine(ctx, comps, n_comps, cfg, 0, ad, ad_len, nullptr, &w, stats, &host), w, proof_words, n_words, "nx_prove_machine_host_narrow");
 }
 
 int nx_machine_claimed_sums(const nx_ctx* ctx, uint32_t* claimed_sums, uint32_t cap_components, uint32_t* n_components) {

@@ -162,6 +162,9 @@ class TreeBuilder {
         DevBuf slab; uint32_t n_cols, log; bool is_evals; uint32_t lo, hi;   // slab: columns [lo, hi) of the group's n_cols (all of them on one GPU)
         // host-resident source (extend_evals_host): the slab is FILLED by the commit, from these host columns, while it transforms
         std::vector<const uint32_t*> host; int coset_order = 0;
+        // narrow upload (NX_COL_*, empty = all NX_COL_U32): the element kind of each host column, its index in the caller's array (a refusal
+        // names it) and the caller's name of that array
+        std::vector<uint8_t> kinds; uint32_t call_col0 = 0; const char* what = nullptr;
         std::vector<std::pair<uint32_t, uint32_t*>> keep;                    // (column of the group, device buffer): its evaluations, cloned before the transform (R4)
     };
     explicit TreeBuilder(CommitmentSchemeProver& c) : cs(c) {}
@@ -175,6 +178,14 @@ class TreeBuilder {
                            const std::vector<std::pair<uint32_t, uint32_t*>>& keep = {}) {
         push(std::move(slab), n_cols, log, true, 0, n_cols);
         groups.back().host.assign(h_cols, h_cols + n_cols); groups.back().coset_order = coset_order; groups.back().keep = keep;
+    }
+    // the same with an element kind per host column (NX_COL_*, kinds may be null = all NX_COL_U32; nx::HostFeed::chunk); call_col0 / what:
+    // where the group's columns start in the caller's array and its name, for the refusal's message
+    void extend_evals_host(DevBuf&& slab, uint32_t n_cols, uint32_t log, const void* const* h_cols, const uint8_t* kinds, int coset_order,
+                           const std::vector<std::pair<uint32_t, uint32_t*>>& keep, uint32_t call_col0, const char* what) {
+        extend_evals_host(std::move(slab), n_cols, log, (const uint32_t* const*)h_cols, coset_order, keep);
+        if (kinds) groups.back().kinds.assign(kinds, kinds + n_cols);
+        groups.back().call_col0 = call_col0; groups.back().what = what;
     }
     // row-sharded prove: the slab holds this GPU's columns [lo, hi) of the group (plan_local_columns)
     void extend_evals_local(DevBuf&& slab, uint32_t n_cols, uint32_t log, uint32_t lo, uint32_t hi) { push(std::move(slab), n_cols, log, true, lo, hi); }

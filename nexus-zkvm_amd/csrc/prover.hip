@@ -289,7 +289,8 @@ int TreeBuilder::commit_begin() {
             const bool leaf = el == max_el;
             // host-resident columns of this run: per column its host source, and what to clone on arrival
             std::vector<const uint32_t*> hsrc(n_run, nullptr); std::vector<uint32_t*> keep_of(n_run, nullptr);
-            bool any_host = false; int coset_order = 0;
+            std::vector<uint8_t> hkind(n_run, (uint8_t)NX_COL_U32); std::vector<uint32_t> hcall(n_run, 0);
+            bool any_host = false, any_kind = false; int coset_order = 0; const char* what = nullptr;
             {
                 uint32_t off = 0;
                 for (size_t g = g0; g < g1; g++) {
@@ -297,6 +298,9 @@ int TreeBuilder::commit_begin() {
                         if (any_host && coset_order != groups[g].coset_order) return set_err(ctx, NX_ERR_ARG, "TreeBuilder: the host columns of one run must share one order");
                         any_host = true; coset_order = groups[g].coset_order;
                         for (uint32_t k = 0; k < groups[g].n_cols; k++) hsrc[off + k] = groups[g].host[k];
+                        for (uint32_t k = 0; k < groups[g].n_cols; k++) hcall[off + k] = groups[g].call_col0 + k;
+                        if (!groups[g].kinds.empty()) { any_kind = true; std::copy(groups[g].kinds.begin(), groups[g].kinds.end(), hkind.begin() + off); }
+                        if (groups[g].what) what = groups[g].what;
                         for (auto& kv : groups[g].keep) { if (kv.first >= groups[g].n_cols) return set_err(ctx, NX_ERR_ARG, "TreeBuilder: keep index outside the group"); keep_of[off + kv.first] = kv.second; }
                     }
                     off += groups[g].n_cols;
@@ -315,7 +319,8 @@ int TreeBuilder::commit_begin() {
                         if (!hsrc[a]) { a++; continue; }
                         uint32_t b2 = a; while (b2 < c0 + nb && hsrc[b2]) b2++;
                         hipEvent_t ready = nullptr;
-                        H_TRY(feed->chunk(hsrc.data() + a, in.data() + a, b2 - a, &ready));
+                        if (any_kind) H_TRY(feed->chunk((const void* const*)hsrc.data() + a, hkind.data() + a, hcall.data() + a, what, in.data() + a, b2 - a, &ready));
+                        else H_TRY(feed->chunk(hsrc.data() + a, in.data() + a, b2 - a, &ready));
                         NX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ready, 0));
                         a = b2;
                     }
@@ -1995,15 +2000,19 @@ int nx_committed_tree_root(const nx_committed_tree* t, uint8_t root[32], uint32_
     return NX_OK;
 }
 
-int nx_prover_tree_commit_host(nx_prover* p, const uint32_t* const* h_cols, int coset_order, const uint32_t* keep_idx, uint32_t n_keep, uint32_t* const* d_keep,
-                               uint8_t root[32]) {
+}  // extern "C" (re-opened below)
+// nx_prover_tree_commit_host and its narrow form: kinds == nullptr is the u32 entry point, unchanged (nx_upload_columns / the u32 feed)
+static int tree_commit_host(nx_prover* p, const void* const* h_cols, const uint8_t* kinds, int coset_order, const uint32_t* keep_idx, uint32_t n_keep,
+                            uint32_t* const* d_keep, uint8_t root[32], const char* fn) {
     NX_GUARD(p ? p->ctx : nullptr);
-    if (!p) return set_err(nullptr, NX_ERR_ARG, "nx_prover_tree_commit_host: NULL prover");
-    if (!p->open) return set_err(p->ctx, NX_ERR_ARG, "nx_prover_tree_commit_host: no tree was begun");
+    const std::string name(fn), what = name + ": h_cols";
+    if (!p) return set_err(nullptr, NX_ERR_ARG, name + ": NULL prover");
+    if (!p->open) return set_err(p->ctx, NX_ERR_ARG, name + ": no tree was begun");
     uint32_t n_total = 0;
     for (auto& r : p->pending) n_total += r.n_cols;
-    if ((n_total && !h_cols) || (n_keep && (!keep_idx || !d_keep))) return set_err(p->ctx, NX_ERR_ARG, "nx_prover_tree_commit_host: NULL argument");
-    for (uint32_t k = 0; k < n_keep; k++) if (keep_idx[k] >= n_total || !d_keep[k]) return set_err(p->ctx, NX_ERR_ARG, "nx_prover_tree_commit_host: keep entry outside the tree (or NULL)");
+    if ((n_total && !h_cols) || (n_keep && (!keep_idx || !d_keep))) return set_err(p->ctx, NX_ERR_ARG, name + ": NULL argument");
+    for (uint32_t k = 0; k < n_keep; k++) if (keep_idx[k] >= n_total || !d_keep[k]) return set_err(p->ctx, NX_ERR_ARG, name + ": keep entry outside the tree (or NULL)");
+    if (kinds) for (uint32_t k = 0; k < n_total; k++) if (kinds[k] > NX_COL_U32_AS_U8) return set_err(p->ctx, NX_ERR_ARG, name + ": unknown column kind");
     const bool sharded = p->cs->dist.on();
     // a rank that fails here (before or inside the commit) tells its peers, which are in — or about to enter — the commit's exchanges
     auto run = [&]() -> int {
@@ -2012,20 +2021,30 @@ int nx_prover_tree_commit_host(nx_prover* p, const uint32_t* const* h_cols, int 
         for (auto& r : p->pending) {
             if (sharded) {
                 // this GPU's columns of the run, uploaded before the commit (the exchange-bound sharded commit gains nothing from the overlap)
-                std::vector<const uint32_t*> hs; std::vector<uint32_t*> ds;
-                for (uint32_t k = r.lo; k < r.hi; k++) { if (!h_cols[first + k]) return set_err(p->ctx, NX_ERR_ARG, "nx_prover_tree_commit_host: NULL host column"); hs.push_back(h_cols[first + k]); ds.push_back(r.slab.p + ((size_t)(k - r.lo) << r.log)); }
-                if (!hs.empty()) NX_TRY(nx_upload_columns(p->ctx, hs.data(), (uint32_t)hs.size(), r.log, ds.data(), coset_order));
+                std::vector<const void*> hs; std::vector<uint32_t*> ds; std::vector<uint8_t> ks;
+                for (uint32_t k = r.lo; k < r.hi; k++) {
+                    if (!h_cols[first + k]) return set_err(p->ctx, NX_ERR_ARG, name + ": NULL host column");
+                    hs.push_back(h_cols[first + k]); ds.push_back(r.slab.p + ((size_t)(k - r.lo) << r.log)); if (kinds) ks.push_back(kinds[first + k]);
+                }
+                if (!hs.empty() && !kinds) NX_TRY(nx_upload_columns(p->ctx, (const uint32_t* const*)hs.data(), (uint32_t)hs.size(), r.log, ds.data(), coset_order));
+                if (!hs.empty() && kinds) {
+                    std::vector<uint32_t> call(hs.size());
+                    for (size_t k = 0; k < call.size(); k++) call[k] = first + r.lo + (uint32_t)k;
+                    NX_TRY(upload_columns_narrow(p->ctx, hs.data(), ks.data(), (uint32_t)hs.size(), r.log, ds.data(), coset_order, call.data(), what.c_str()));
+                }
                 for (uint32_t k = 0; k < n_keep; k++)
                     if (keep_idx[k] >= first + r.lo && keep_idx[k] < first + r.hi) NX_TRY(nx_copy(p->ctx, d_keep[k], r.slab.p + ((size_t)(keep_idx[k] - first - r.lo) << r.log), (size_t)1 << r.log));
                 tb.extend_evals_local(std::move(r.slab), r.n_cols, r.log, r.lo, r.hi);
             } else {
-                for (uint32_t k = 0; k < r.n_cols; k++) if (!h_cols[first + k]) return set_err(p->ctx, NX_ERR_ARG, "nx_prover_tree_commit_host: NULL host column");
+                for (uint32_t k = 0; k < r.n_cols; k++) if (!h_cols[first + k]) return set_err(p->ctx, NX_ERR_ARG, name + ": NULL host column");
                 std::vector<std::pair<uint32_t, uint32_t*>> keep;
                 for (uint32_t k = 0; k < n_keep; k++) if (keep_idx[k] >= first && keep_idx[k] < first + r.n_cols) keep.push_back({keep_idx[k] - first, d_keep[k]});
-                tb.extend_evals_host(std::move(r.slab), r.n_cols, r.log, h_cols + first, coset_order, keep);
+                if (kinds) tb.extend_evals_host(std::move(r.slab), r.n_cols, r.log, h_cols + first, kinds + first, coset_order, keep, first, what.c_str());
+                else tb.extend_evals_host(std::move(r.slab), r.n_cols, r.log, (const uint32_t* const*)h_cols + first, coset_order, keep);
             }
             first += r.n_cols;
         }
+        // the root enters the transcript only at the end of the commit (TreeBuilder::commit_end): a refused chunk returns before it
         return tb.commit(p->channel);
     };
     p->ctx->symmetric_failure = false;
@@ -2034,6 +2053,18 @@ int nx_prover_tree_commit_host(nx_prover* p, const uint32_t* const* h_cols, int 
     if (rc != NX_OK) { if (p->has_comm && p->comm_copy.world > 1 && p->comm_copy.abort && !p->ctx->symmetric_failure) p->comm_copy.abort(p->comm_copy.user); return rc; }
     if (root) memcpy(root, p->cs->trees.back().root.w, 32);
     return NX_OK;
+}
+extern "C" {
+
+int nx_prover_tree_commit_host(nx_prover* p, const uint32_t* const* h_cols, int coset_order, const uint32_t* keep_idx, uint32_t n_keep, uint32_t* const* d_keep,
+                               uint8_t root[32]) {
+    return tree_commit_host(p, (const void* const*)h_cols, nullptr, coset_order, keep_idx, n_keep, d_keep, root, "nx_prover_tree_commit_host");
+}
+
+int nx_prover_tree_commit_host_narrow(nx_prover* p, const void* const* h_cols, const uint8_t* kinds, int coset_order, const uint32_t* keep_idx, uint32_t n_keep,
+                                      uint32_t* const* d_keep, uint8_t root[32]) {
+    if (p && !h_cols) return set_err(p->ctx, NX_ERR_ARG, "nx_prover_tree_commit_host_narrow: NULL argument");
+    return tree_commit_host(p, h_cols, kinds, coset_order, keep_idx, n_keep, d_keep, root, "nx_prover_tree_commit_host_narrow");
 }
 
 int nx_prover_prove(nx_prover* p, const nx_air_component* comps, uint32_t n_comps, uint32_t** proof_words, size_t* n_words, nx_prove_stats* stats) {

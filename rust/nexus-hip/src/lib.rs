@@ -17,7 +17,7 @@
 #![allow(clippy::missing_safety_doc)]
 
 use nexus_hip_sys as sys;
-use std::ffi::CStr;
+use std::ffi::{c_void, CStr};
 use std::marker::PhantomData;
 use std::sync::{Mutex, MutexGuard, OnceLock};
 
@@ -368,6 +368,27 @@ impl Session {
         let dst: Vec<*mut u32> = keep.iter().map(|k| k.1).collect();
         let mut r = [0u8; 32];
         try_check(self.ctx, unsafe { sys::nx_prover_tree_commit_host(self.p, host_cols.as_ptr(), coset_order as i32, idx.as_ptr(), idx.len() as u32, dst.as_ptr(), r.as_mut_ptr()) })?;
+        Ok(r)
+    }
+    /// `upload` for host columns of byte or half-word limbs: each entry is (column pointer, `sys::NX_COL_*` kind).  `NX_COL_U8` /
+    /// `NX_COL_U16` columns hold `u8` / `u16` and cross PCIe as they are; `NX_COL_U32_AS_U8` / `NX_COL_U32_AS_U16` columns hold `u32`
+    /// (the layout of the reference's `IntoBaseFields for u32`) and are packed on host threads, a value that does not fit is an error.
+    pub fn upload_narrow(&mut self, host_cols: &[(*const c_void, u8)], log_size: u32, dev_cols: &[*mut u32], coset_order: bool) -> Result<(), HipError> {
+        let ptrs: Vec<*const c_void> = host_cols.iter().map(|c| c.0).collect();
+        let kinds: Vec<u8> = host_cols.iter().map(|c| c.1).collect();
+        try_check(self.ctx, unsafe { sys::nx_upload_columns_narrow(self.ctx, ptrs.as_ptr(), kinds.as_ptr(), ptrs.len() as u32, log_size, dev_cols.as_ptr(), coset_order as i32) })
+    }
+    /// `tree_commit_host` with a `sys::NX_COL_*` kind per host column (see `upload_narrow`).  A refused value leaves the transcript as it
+    /// was: `tree_begin` the same tree again and commit corrected columns.
+    pub fn tree_commit_host_narrow(&mut self, host_cols: &[(*const c_void, u8)], coset_order: bool, keep: &[(u32, *mut u32)]) -> Result<[u8; 32], HipError> {
+        let ptrs: Vec<*const c_void> = host_cols.iter().map(|c| c.0).collect();
+        let kinds: Vec<u8> = host_cols.iter().map(|c| c.1).collect();
+        let idx: Vec<u32> = keep.iter().map(|k| k.0).collect();
+        let dst: Vec<*mut u32> = keep.iter().map(|k| k.1).collect();
+        let mut r = [0u8; 32];
+        try_check(self.ctx, unsafe {
+            sys::nx_prover_tree_commit_host_narrow(self.p, ptrs.as_ptr(), kinds.as_ptr(), coset_order as i32, idx.as_ptr(), idx.len() as u32, dst.as_ptr(), r.as_mut_ptr())
+        })?;
         Ok(r)
     }
     /// `n_cols` device columns of 2^log_size words that live as long as the session (the kept evaluations of the trace columns the
