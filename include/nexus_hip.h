@@ -79,10 +79,8 @@ int nx_ctx_set_hash_mode(nx_ctx* ctx, int mode);
  * measured best): "fft.kmax" (most layers of a non-first FFT pass, 1..11), "fft.fused" (fused middle launch of the LDE), "merkle.subtree"
  * (highest level built by the fused sub-tree launch; 0 = one launch per level), "merkle.top" (the level, 1..10, from which ONE block
  * builds the rest of a tree), "merkle.pair_levels" (two node-only levels per launch
- * above it), "commit.pipe_cols" (leaf hashing beside the LDE in
- * groups of this many columns; 0 = off), "fri.device_channel", "fri.tail" (0 = off, 1 = the FRI layers of <= 2^11 points in one launch,
- * 2..11 = from 2^that many points), "logup.scan_tiled", "logup.per_column", "logup.staged" (nx_logup_cols requests
- * every read of a group of 8 fractions before it uses the first value; 0 = reads where they are used).  "host.pack_threads" (1..64; default
+ * above it), "fri.device_channel", "fri.tail" (0 = off, 1 = the FRI layers of <= 2^11 points in one launch,
+ * 2..11 = from 2^that many points), "logup.scan_tiled", "logup.per_column".  "host.pack_threads" (1..64; default
  * min(16, hardware threads)): host threads that pack NX_COL_U32_AS_U16 / NX_COL_U32_AS_U8 columns of the narrow upload entry points.
  * Unknown names and out-of-range values are NX_ERR_ARG.
  * None of them changes a result: proofs, roots and transforms are bit-identical under every setting. */

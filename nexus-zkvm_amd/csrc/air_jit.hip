@@ -123,7 +123,7 @@ static uint32_t segment_budget(const nx_ctx* ctx) {
 // sum_k alpha^k value_k — what machine.hip's emit_den and a recorder's lowering of LookupElements::combine produce, 200 terms long for the
 // reference's widest relation.  Emitted literally a term is 4 reduced products and 4 reduced sums (~36 VALU instructions); fused it is 4
 // raw 64-bit multiply-adds (v_mad_u64_u32 with its free 64-bit addend) into a lazy accumulator of D that is folded every 4 terms and
-// reduced ONCE, when D is next read — the same residue, a third of the instructions.  `NX_AIR_FUSE_DOT=0` emits the literal form (A/B).
+// reduced ONCE, when D is next read — the same residue, a third of the instructions.
 struct RegRange { uint32_t reg, w; };
 static void instr_ranges(const nx_cinstr& in, std::vector<RegRange>* reads, RegRange* write) {
     reads->clear(); *write = {0, 0};
@@ -141,11 +141,9 @@ static void instr_ranges(const nx_cinstr& in, std::vector<RegRange>* reads, RegR
     default: break;
     }
 }
-static bool fuse_dot_enabled() { static const bool on = [] { const char* e = getenv("NX_AIR_FUSE_DOT"); return !(e && *e == '0'); }(); return on; }
 struct DotFusion { std::vector<char> skip, fused; };      // by position in `keep`: the MULEB that is not emitted, the ADDE that becomes 4 multiply-adds
 static DotFusion find_dot_fusions(const nx_cinstr* prog, const std::vector<uint32_t>& keep, uint32_t n_regs) {
     DotFusion f; f.skip.assign(keep.size(), 0); f.fused.assign(keep.size(), 0);
-    if (!fuse_dot_enabled()) return f;
     std::vector<char> live(n_regs + 8, 0);             // backward: is the register read again before it is rewritten (within this kernel)?
     std::vector<RegRange> reads; RegRange wr;
     auto disjoint = [](uint32_t a, uint32_t b) { return a + 4 <= b || b + 4 <= a; };

@@ -29,7 +29,6 @@ int stage(nx_ctx* ctx, const void* h_src, size_t bytes, void** d_out) {
     if (ctx->scratch_off + need > ctx->scratch_size) {
         // wrap: make sure every earlier consumer of the ring has finished
         NX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        NX_HIP(ctx, hipStreamSynchronize(ctx->hash_stream));
         for (int i = 0; i < 3; i++) NX_HIP(ctx, hipStreamSynchronize(ctx->side[i]));
         ctx->scratch_off = 0;
     }
@@ -177,18 +176,17 @@ static hipEvent_t get_event(nx_ctx* ctx) {
     if (!ctx->event_pool.empty()) { hipEvent_t e = ctx->event_pool.back(); ctx->event_pool.pop_back(); return e; }
     hipEvent_t e; (void)hipEventCreate(&e); return e;
 }
-KTimer::KTimer(nx_ctx* c, int kind, uint64_t bytes, hipStream_t on_stream) : ctx(c), idx(-1), stream(on_stream ? on_stream : c->stream) {
+KTimer::KTimer(nx_ctx* c, int kind, uint64_t bytes) : ctx(c), idx(-1) {
     if (!c->timing) return;
     nx_ctx::Span s; s.e0 = get_event(c); s.e1 = get_event(c); s.kind = kind;
-    (void)hipEventRecord(s.e0, stream);
+    (void)hipEventRecord(s.e0, c->stream);
     c->kind_bytes[kind] += bytes;
     idx = (int)c->spans.size();
     c->spans.push_back(s);
 }
-KTimer::~KTimer() { if (idx >= 0) (void)hipEventRecord(ctx->spans[idx].e1, stream); }
+KTimer::~KTimer() { if (idx >= 0) (void)hipEventRecord(ctx->spans[idx].e1, ctx->stream); }
 void timing_flush(nx_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipStreamSynchronize(ctx->hash_stream);
     for (auto& s : ctx->spans) {
         float ms = 0; (void)hipEventElapsedTime(&ms, s.e0, s.e1);
         ctx->kind_ms[s.kind] += ms;
@@ -321,15 +319,12 @@ static nx_options options_from_env() {
     o.merkle_subtree = clampi(env_int("NX_MERKLE_SUBTREE", 14), 0, 30);   // profiles/r06_merkle_top_ab.jsonl: top 7 / subtree 14 against 10 / 17
     o.merkle_top = clampi(env_int("NX_MERKLE_TOP", 7), 1, 10);
     o.merkle_pair_levels = env_int("NX_MERKLE_PAIR_LEVELS", 1) != 0;
-    { int x = env_int("NX_PIPE_COLS", 0); o.commit_pipe_cols = x < 16 ? 0 : (x / 16) * 16; }
     o.fri_device_channel = env_int("NX_FRI_DEVICE_CHANNEL", 1) != 0;
     o.fri_tail = clampi(env_int("NX_FRI_TAIL", 1), 0, 11);
     o.logup_scan_tiled = env_int("NX_LOGUP_SCAN_TILED", 1) != 0;
-    o.logup_staged = env_int("NX_LOGUP_STAGED", 1) != 0;
     o.logup_per_column = env_int("NX_LOGUP_PER_COLUMN", 0) != 0;
     o.machine_reuse_pre = env_int("NX_MACHINE_REUSE_PREPROCESSED", 0) != 0;
     o.machine_logup_program = env_int("NX_MACHINE_LOGUP_PROGRAM", 0) != 0;
-    o.machine_queue_trees = env_int("NX_MACHINE_QUEUE_TREES", 0) != 0;   // measured: no gain (profiles/r05_queue_trees_ab.txt)
     o.host_pack_threads = clampi((int)std::thread::hardware_concurrency(), 1, 16);   // a GPU box grants a command 16 CPUs
     return o;
 }
@@ -351,14 +346,11 @@ static const OptEntry k_options[] = {
     {"merkle.subtree", &nx_options::merkle_subtree, 0, 30},
     {"merkle.top", &nx_options::merkle_top, 1, 10},
     {"merkle.pair_levels", &nx_options::merkle_pair_levels, 0, 1},
-    {"commit.pipe_cols", &nx_options::commit_pipe_cols, 0, 1 << 20},
     {"fri.device_channel", &nx_options::fri_device_channel, 0, 1},
     {"fri.tail", &nx_options::fri_tail, 0, 11},
     {"logup.scan_tiled", &nx_options::logup_scan_tiled, 0, 1},
-    {"logup.staged", &nx_options::logup_staged, 0, 1},
     {"logup.per_column", &nx_options::logup_per_column, 0, 1},
     {"machine.reuse_preprocessed", &nx_options::machine_reuse_pre, 0, 1},
-    {"machine.queue_trees", &nx_options::machine_queue_trees, 0, 1},
     {"machine.logup_program", &nx_options::machine_logup_program, 0, 1},
     {"host.pack_threads", &nx_options::host_pack_threads, 1, 64},
 };
@@ -368,7 +360,6 @@ int nx_ctx_set_option(nx_ctx* ctx, const char* name, int64_t value) {
         if (!strcmp(e.name, name)) {
             if (value < e.lo || value > e.hi) return set_err(ctx, NX_ERR_ARG, std::string("nx_ctx_set_option: value out of range for ") + name);
             ctx->opt.*(e.field) = (int)value;
-            if (e.field == &nx_options::commit_pipe_cols) ctx->opt.commit_pipe_cols = value < 16 ? 0 : (int)(value / 16) * 16;   // whole 16-column hash blocks, like NX_PIPE_COLS
             return NX_OK;
         }
     return set_err(ctx, NX_ERR_ARG, std::string("nx_ctx_set_option: unknown option ") + name);
@@ -410,10 +401,8 @@ int nx_ctx_create(int device, nx_ctx** out) {
     for (int i = 0; i < 4; i++) { c->kind_ms[i] = 0; c->kind_bytes[i] = 0; }
     NX_HIP(nullptr, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     c->cur = c->stream;
-    NX_HIP(nullptr, hipStreamCreateWithFlags(&c->hash_stream, hipStreamNonBlocking));
     NX_HIP(nullptr, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     NX_HIP(nullptr, hipStreamCreateWithFlags(&c->perm_stream, hipStreamNonBlocking));
-    NX_HIP(nullptr, hipEventCreateWithFlags(&c->hash_ev, hipEventDisableTiming));
     NX_HIP(nullptr, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
     for (int i = 0; i < 3; i++) {
         NX_HIP(nullptr, hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking));
@@ -444,7 +433,6 @@ void nx_ctx_destroy(nx_ctx* ctx) {
     for (auto& kv : ctx->live_pinned) (void)hipHostFree(kv.first);
     for (int i = 0; i < 3; i++) { (void)hipStreamDestroy(ctx->side[i]); (void)hipEventDestroy(ctx->join_ev[i]); }
     (void)hipEventDestroy(ctx->fork_ev);
-    (void)hipStreamDestroy(ctx->hash_stream); (void)hipEventDestroy(ctx->hash_ev);
     (void)hipStreamDestroy(ctx->copy_stream); (void)hipStreamDestroy(ctx->perm_stream);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -457,7 +445,7 @@ int nx_ctx_set_hash_mode(nx_ctx* ctx, int mode) {
     return NX_OK;
 }
 
-int nx_sync(nx_ctx* ctx) { NX_GUARD(ctx); if (!ctx) return set_err(nullptr, NX_ERR_ARG, "nx_sync: NULL context"); NX_HIP(ctx, hipStreamSynchronize(ctx->stream)); NX_HIP(ctx, hipStreamSynchronize(ctx->hash_stream)); return NX_OK; }
+int nx_sync(nx_ctx* ctx) { NX_GUARD(ctx); if (!ctx) return set_err(nullptr, NX_ERR_ARG, "nx_sync: NULL context"); NX_HIP(ctx, hipStreamSynchronize(ctx->stream)); return NX_OK; }
 int nx_ctx_trim(nx_ctx* ctx) { NX_GUARD(ctx); if (!ctx) return set_err(nullptr, NX_ERR_ARG, "nx_ctx_trim: NULL context"); NX_TRY(nx_sync(ctx)); dev_cache_release(ctx); pack_ring_release(ctx); return NX_OK; }
 void* nx_ctx_stream(nx_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 

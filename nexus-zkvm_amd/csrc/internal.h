@@ -29,14 +29,11 @@ struct nx_options {
     int merkle_fused;             // "merkle.fused": 0 = off, else the smallest log size from which the tree of <= 4 columns of one size (composition tree, FRI layers) gets its leaf hash — for a FRI layer also the fold — and 6 levels in one launch (merkle_fused_kernel)
     int merkle_top;               // "merkle.top": highest level the one-block top launch (merkle_top_kernel) starts from: 2^top nodes, <= 10
     int merkle_subtree; int merkle_pair_levels;           // "merkle.subtree": highest tree level built by the fused subtree launch (0 = one launch per level)
-    int commit_pipe_cols;         // "commit.pipe_cols": leaf hashing of finished column groups of this many columns beside the next group's LDE (0 = off)
     int fri_device_channel;       // "fri.device_channel": FRI commit phase with the channel on the device
     int fri_tail;                 // "fri.tail": last FRI layers in one launch: 0 = off, 1 = from 2^11 points (FRI_TAIL_LOG), 2 .. 11 = from 2^that many
     int logup_scan_tiled;         // "logup.scan_tiled": finalize_last as coalesced tiles
-    int logup_staged;             // "logup.staged": nx_logup_cols requests every read of a group of fractions up front (values parked in LDS)
     int logup_per_column;         // "logup.per_column": one nx_logup_col launch per column instead of nx_logup_cols
     int machine_logup_program;    // "machine.logup_program": nx_prove_machine builds the interaction trace of every wide-tuple component (NX_LOGUP_TUPLES != 0) from its recorded relation entries (nx_logup_program) instead of nx_logup_cols (same bytes; components with expression numerators always do)
-    int machine_queue_trees;      // "machine.queue_trees": nx_prove_machine queues the preprocessed and the main tree builds before fetching the first root (1) or commits them one after the other (0; A/B)
     int machine_reuse_pre;        // "machine.reuse_preprocessed": nx_prove_machine keeps the committed preprocessed tree of a statement shape in the context and adopts it in later proofs (nx_prover_tree_adopt's rule; default 0: every proof commits it afresh, as the reference does)
     int air_degree_split;         // "air.degree_split": constraints of degree <= 3 of a component with a bound > 1 are evaluated on the log_size + 1 domain
     int host_pack_threads;        // "host.pack_threads": host threads that pack NX_COL_U32_AS_* columns (HostFeed)
@@ -52,8 +49,6 @@ struct nx_ctx {
     hipEvent_t fork_ev, join_ev[3];
     hipStream_t cur;   // stream the FFT launchers enqueue on (== stream outside a forked region)
     hipStream_t copy_stream, perm_stream;   // host-trace feed (HostFeed): PCIe copies / the R3 permutation behind them, next to the commit's kernels
-    hipStream_t hash_stream;   // leaf hashing of finished column groups runs here, next to the LDE of the next group
-    hipEvent_t hash_ev;
     int hash_mode;
     int n_cus;       // compute units of the device
     std::string err;
@@ -255,8 +250,8 @@ int transpose_blocks(nx_ctx* ctx, uint32_t* full, uint64_t col_stride, uint32_t*
 
 // Event-pair span on ctx->stream, recorded only when ctx->timing is on; resolved by timing_flush.
 struct KTimer {
-    nx_ctx* ctx; int idx; hipStream_t stream;
-    KTimer(nx_ctx* c, int kind, uint64_t algorithmic_bytes, hipStream_t on_stream = nullptr);
+    nx_ctx* ctx; int idx;
+    KTimer(nx_ctx* c, int kind, uint64_t algorithmic_bytes);
     ~KTimer();
 };
 void timing_flush(nx_ctx* ctx);  // synchronises the stream and folds spans into kind_ms[]
@@ -267,8 +262,9 @@ int fft_interpolate(nx_ctx* ctx, const nx_twiddles* tw, ColSet cols, uint32_t n_
 int fft_evaluate(nx_ctx* ctx, const nx_twiddles* tw, ColSet polys, uint32_t n_cols, uint32_t log_size,
                  uint32_t log_expand, ColSet out);
 
-// Pipelined tree build (merkle.hip): the leaf layer is a per-row Blake2s chain over the largest columns in commit order,
-// so finished column groups can be absorbed (on ctx->hash_stream) while the main stream already transforms the next group.
+// Incremental tree build (merkle.hip): the leaf layer is a per-row Blake2s chain over the largest columns in commit order, so the
+// columns are absorbed in 16-column blocks, in stream order, as their LDE is enqueued (the column-sharded commit chains its shards with
+// the same kernel: nx_merkle_leaf_chain).
 // FRI tail (merkle.hip): the last FRI layers (line layers of <= 2^FRI_TAIL_LOG points) committed and folded in one launch with the
 // channel on the device.
 constexpr int FRI_TAIL_LOG = 11, FRI_TAIL_MAX_LAYERS = 16;   // 2^12 and up: one CU is slower than the per-layer launches (measured)
@@ -297,7 +293,6 @@ struct TreePipe {
     uint32_t max_log = 0, total_leaf_cols = 0, absorbed = 0;
     std::vector<const uint32_t*> pending;   // columns handed in but not yet hashed (kept until a 16-column block is complete)
     bool any_launch = false;
-    bool side_stream = false;              // hash on ctx->hash_stream behind the next column group's LDE (NX_PIPE_COLS); else in stream order
 };
 int tree_pipe_begin(nx_ctx* ctx, uint32_t max_log, uint32_t total_leaf_cols, TreePipe* tp);
 int tree_pipe_absorb(nx_ctx* ctx, TreePipe* tp, const uint32_t* const* d_cols, uint32_t n_cols, bool flush);

@@ -98,41 +98,37 @@ struct LogupBatchFrac { u32 first_col, n_cols, first_ap, out_col; const u32* mul
 // 3 multiplications per element): 57 -> 20 + 3 + 37/8 multiplications per fraction.  Same values: an inverse is unique; a zero
 // denominator (norm 0) still gives 0 like m_inv(0), and does not poison its group.
 constexpr int LOGUP_GROUP = 8;
-// STAGED: every memory read of a group — the tuple columns of its 8 fractions (up to LOGUP_TMAX of them) and their multiplicities — is
+// Every memory read of a group — the tuple columns of its 8 fractions (up to LOGUP_TMAX of them) and their multiplicities — is
 // requested before the first value is used.  The fractions' tuple widths are run-time values, so the values cannot sit in (statically
 // indexed) registers: each lane parks its own row's values in LDS (stage[column][lane], read back by the same lane: no barrier) and the
-// combine loop indexes that.  Without it every column read of every fraction is a dependent scalar load (the pointer) + vector load with
+// combine loop indexes that.  Read where it is used, every column value was a dependent scalar load (the pointer) + vector load with
 // a full wait in between: the kernel ran at the latency of ~500 serial round trips per lane (1.3 TB/s written at 250 fractions).
 constexpr int LOGUP_TMAX = 32;            // 32 KB of LDS per 256-lane block: 5 blocks per CU, what the 88 VGPRs allow anyway
-template <bool STAGED>
 __global__ __launch_bounds__(256) void logup_cols_kernel(const LogupBatchFrac* __restrict__ fr, u32 n_fracs, const u32* const* __restrict__ tuple_cols,
                                                          const u32* __restrict__ ap /*4 words each*/, u32* const* __restrict__ out /*4 per logup column*/, u32 n) {
-    __shared__ u32 stage[STAGED ? LOGUP_TMAX * 256 : 1];
+    __shared__ u32 stage[LOGUP_TMAX * 256];
     const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;                                               // no barrier below: a lane only reads back what it staged itself
     QM31 run = q_zero();
     for (u32 j0 = 0; j0 < n_fracs; j0 += LOGUP_GROUP) {
         QM31 den[LOGUP_GROUP]; CM31 dd[LOGUP_GROUP]; u32 nrm[LOGUP_GROUP], pre[LOGUP_GROUP], mv[LOGUP_GROUP];
-        bool staged = false; u32 c0 = 0;
-        if (STAGED) {
 #pragma unroll
-            for (int g = 0; g < LOGUP_GROUP; g++) {                   // the multiplicities first: in flight with everything below.  Branch-free
-                const u32 jg = j0 + g < n_fracs ? j0 + g : n_fracs - 1;   // (a select, not a jump: a join would wait for the load): a fraction
-                const u32* mp = fr[jg].mult;                          // without one reads a word of the first output column and drops it
-                mv[g] = gld((mp ? mp : (const u32*)out[0]) + r);
-            }
-            const u32 jl = (j0 + LOGUP_GROUP < n_fracs ? j0 + LOGUP_GROUP : n_fracs) - 1;
-            c0 = fr[j0].first_col;
-            const u32 T = fr[jl].first_col + fr[jl].n_cols - c0;      // the group's tuple columns are consecutive in the table (logup_cols_launch)
-            staged = T <= (u32)LOGUP_TMAX;                            // uniform; a wider group reads its columns where it uses them
-            if (staged) {
-                for (u32 t0 = 0; t0 < T; t0 += 8) {
-                    u32 v[8];
+        for (int g = 0; g < LOGUP_GROUP; g++) {                       // the multiplicities first: in flight with everything below.  Branch-free
+            const u32 jg = j0 + g < n_fracs ? j0 + g : n_fracs - 1;       // (a select, not a jump: a join would wait for the load): a fraction
+            const u32* mp = fr[jg].mult;                              // without one reads a word of the first output column and drops it
+            mv[g] = gld((mp ? mp : (const u32*)out[0]) + r);
+        }
+        const u32 jl = (j0 + LOGUP_GROUP < n_fracs ? j0 + LOGUP_GROUP : n_fracs) - 1;
+        const u32 c0 = fr[j0].first_col;
+        const u32 T = fr[jl].first_col + fr[jl].n_cols - c0;          // the group's tuple columns are consecutive in the table (logup_cols_launch)
+        const bool staged = T <= (u32)LOGUP_TMAX;                     // uniform; a wider group reads its columns where it uses them
+        if (staged) {
+            for (u32 t0 = 0; t0 < T; t0 += 8) {
+                u32 v[8];
 #pragma unroll
-                    for (u32 i = 0; i < 8; i++) { const u32 t = t0 + i < T ? t0 + i : T - 1; v[i] = gld(tuple_cols[c0 + t] + r); }
+                for (u32 i = 0; i < 8; i++) { const u32 t = t0 + i < T ? t0 + i : T - 1; v[i] = gld(tuple_cols[c0 + t] + r); }
 #pragma unroll
-                    for (u32 i = 0; i < 8; i++) { const u32 t = t0 + i < T ? t0 + i : T - 1; stage[t * 256 + threadIdx.x] = v[i]; }
-                }
+                for (u32 i = 0; i < 8; i++) { const u32 t = t0 + i < T ? t0 + i : T - 1; stage[t * 256 + threadIdx.x] = v[i]; }
             }
         }
         // phase 1, once per source of the values (the branch is taken per group, not per column read)
@@ -156,7 +152,7 @@ __global__ __launch_bounds__(256) void logup_cols_kernel(const LogupBatchFrac* _
                 pre[g] = g ? m_mul(pre[g - 1], nz) : nz;
             }
         };
-        if (STAGED && staged) denominators([&](u32 col) { return stage[(col - c0) * 256 + threadIdx.x]; });
+        if (staged) denominators([&](u32 col) { return stage[(col - c0) * 256 + threadIdx.x]; });
         else denominators([&](u32 col) { return gld(tuple_cols[col] + r); });
         u32 inv = m_inv(pre[LOGUP_GROUP - 1]);
 #pragma unroll
@@ -171,7 +167,7 @@ __global__ __launch_bounds__(256) void logup_cols_kernel(const LogupBatchFrac* _
             if (j0 + g < n_fracs) {
                 const u32 j = j0 + g;
                 const LogupBatchFrac f = fr[j];
-                const u32 mval = f.mult ? (STAGED ? mv[g] : gld(f.mult + r)) : 0u;
+                const u32 mval = f.mult ? mv[g] : 0u;
                 if ((f.scale.a.b | f.scale.b.a | f.scale.b.b) == 0) {          // uniform: a base-field numerator (+-1, a multiplicity): it rides on 1 / |D|^2,
                     const u32 nm = f.mult ? m_mul(f.scale.a.a, mval) : f.scale.a.a;     // and the fraction goes straight into the running sum's accumulators
                     const u32 sc = m_mul(pre[g], nm);
@@ -495,12 +491,8 @@ static int logup_cols_launch(nx_ctx* ctx, uint32_t log_size, const nx_logup_frac
     }
     const u32 n = 1u << log_size;
     if (e == hipSuccess) {
-        if (ctx->opt.logup_staged)
-            hipLaunchKernelGGL(logup_cols_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const LogupBatchFrac*)blob, n_fracs, (const u32* const*)(blob + o_cols),
-                               (const u32*)(blob + o_ap), (u32* const*)(blob + o_out), n);
-        else
-            hipLaunchKernelGGL(logup_cols_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const LogupBatchFrac*)blob, n_fracs, (const u32* const*)(blob + o_cols),
-                               (const u32*)(blob + o_ap), (u32* const*)(blob + o_out), n);
+        hipLaunchKernelGGL(logup_cols_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const LogupBatchFrac*)blob, n_fracs, (const u32* const*)(blob + o_cols),
+                           (const u32*)(blob + o_ap), (u32* const*)(blob + o_out), n);
         e = hipGetLastError();
     }
     dev_free(ctx, blob);   // stream-ordered: reused only by later work on this stream

@@ -696,15 +696,14 @@ __global__ void grind_kernel(const u32* __restrict__ digest, u32 pow_bits, u64 b
 
 int merkle_layer(nx_ctx* ctx, ColSet cols, u32 n_cols, const u32* prev, u32* out, u32 log);
 
-int leaf_chain_launch(nx_ctx* ctx, hipStream_t stream, ColSet cs, u32 n_cols, u32 col_offset, u32 total_cols, const u32* state_in, u32* state_out,
-                      u64 row_begin, u64 n_rows) {
-    KTimer timer(ctx, NX_T_MERKLE, n_rows * (4ull * n_cols + 64), stream);
+int leaf_chain_launch(nx_ctx* ctx, ColSet cs, u32 n_cols, u32 col_offset, u32 total_cols, const u32* state_in, u32* state_out, u64 row_begin, u64 n_rows) {
+    KTimer timer(ctx, NX_T_MERKLE, n_rows * (4ull * n_cols + 64));
     dim3 block(256);
     dim3 grid((unsigned)((n_rows + 255) / 256));
     if (ctx->hash_mode == NX_HASH_BLAKE2S)
-        hipLaunchKernelGGL(merkle_leaf_chain_kernel<0>, grid, block, 0, stream, cs, n_cols, col_offset, total_cols, state_in, state_out, row_begin, n_rows);
+        hipLaunchKernelGGL(merkle_leaf_chain_kernel<0>, grid, block, 0, ctx->stream, cs, n_cols, col_offset, total_cols, state_in, state_out, row_begin, n_rows);
     else
-        hipLaunchKernelGGL(merkle_leaf_chain_kernel<1>, grid, block, 0, stream, cs, n_cols, col_offset, total_cols, state_in, state_out, row_begin, n_rows);
+        hipLaunchKernelGGL(merkle_leaf_chain_kernel<1>, grid, block, 0, ctx->stream, cs, n_cols, col_offset, total_cols, state_in, state_out, row_begin, n_rows);
     NX_LAUNCH_CHECK(ctx);
     return NX_OK;
 }
@@ -807,23 +806,16 @@ int tree_pipe_begin(nx_ctx* ctx, uint32_t max_log, uint32_t total_leaf_cols, Tre
     return NX_OK;
 }
 
-// Hash every complete 16-column block handed in so far (all of them when `flush`): ordered after the work already on the
-// main stream (the LDE that produced the columns), executed on the hash stream.
+// Hash every complete 16-column block handed in so far (all of them when `flush`), in stream order behind the LDE that produced them.
 int tree_pipe_absorb(nx_ctx* ctx, TreePipe* tp, const uint32_t* const* d_cols, uint32_t n_cols, bool flush) {
     for (uint32_t i = 0; i < n_cols; i++) tp->pending.push_back(d_cols[i]);
     if (tp->absorbed + tp->pending.size() > tp->total_leaf_cols) return set_err(ctx, NX_ERR_ARG, "tree_pipe_absorb: more columns than announced");
     const bool is_end = tp->absorbed + tp->pending.size() == tp->total_leaf_cols;
     size_t take = (flush || is_end) && is_end ? tp->pending.size() : (tp->pending.size() / 16) * 16;
     if (take == 0) return NX_OK;
-    ColSet cs; NX_TRY(make_colset(ctx, tp->pending.data(), (uint32_t)take, &cs));   // pointer table staged on the main stream
-    hipStream_t hs = ctx->stream;
-    if (tp->side_stream) {
-        NX_HIP(ctx, hipEventRecord(ctx->hash_ev, ctx->stream));
-        NX_HIP(ctx, hipStreamWaitEvent(ctx->hash_stream, ctx->hash_ev, 0));
-        hs = ctx->hash_stream;
-    }
+    ColSet cs; NX_TRY(make_colset(ctx, tp->pending.data(), (uint32_t)take, &cs));
     u32* leaves = tp->tree->layers[tp->max_log];
-    NX_TRY(leaf_chain_launch(ctx, hs, cs, (u32)take, tp->absorbed, tp->total_leaf_cols, tp->absorbed ? leaves : nullptr, leaves, 0,
+    NX_TRY(leaf_chain_launch(ctx, cs, (u32)take, tp->absorbed, tp->total_leaf_cols, tp->absorbed ? leaves : nullptr, leaves, 0,
                              (u64)1 << tp->max_log));
     tp->absorbed += (uint32_t)take;
     tp->pending.erase(tp->pending.begin(), tp->pending.begin() + take);
@@ -834,11 +826,6 @@ int tree_pipe_absorb(nx_ctx* ctx, TreePipe* tp, const uint32_t* const* d_cols, u
 int tree_pipe_finish(nx_ctx* ctx, TreePipe* tp, const uint32_t* const* d_small_cols, const uint32_t* small_logs, uint32_t n_small, nx_tree** out) {
     int rc = tree_pipe_absorb(ctx, tp, nullptr, 0, true);
     if (rc == NX_OK && tp->absorbed != tp->total_leaf_cols) rc = set_err(ctx, NX_ERR_ARG, "tree_pipe_finish: fewer leaf columns than announced");
-    if (rc == NX_OK && tp->side_stream) {
-        hipError_t e = hipEventRecord(ctx->hash_ev, ctx->hash_stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->hash_ev, 0);
-        if (e != hipSuccess) rc = hip_fail(ctx, e, "tree_pipe_finish", __FILE__, __LINE__);
-    }
     if (rc == NX_OK) {
         std::vector<uint32_t> order(n_small);
         std::iota(order.begin(), order.end(), 0u);
@@ -848,7 +835,7 @@ int tree_pipe_finish(nx_ctx* ctx, TreePipe* tp, const uint32_t* const* d_small_c
         KTimer timer(ctx, NX_T_MERKLE, (uint64_t)96 << tp->max_log);
         rc = build_inner_layers(ctx, tp->tree, tp->max_log, sorted, logs);
     }
-    if (rc != NX_OK) { (void)hipStreamSynchronize(ctx->hash_stream); nx_tree_destroy(tp->tree); tp->tree = nullptr; return rc; }
+    if (rc != NX_OK) { nx_tree_destroy(tp->tree); tp->tree = nullptr; return rc; }
     *out = tp->tree; tp->tree = nullptr;
     return NX_OK;
 }
@@ -930,7 +917,7 @@ int nx_merkle_leaf_chain(nx_ctx* ctx, const uint32_t* const* d_cols, uint32_t n_
     if (log_size > 30 || row_begin + n_rows > ((uint64_t)1 << log_size)) return set_err(ctx, NX_ERR_ARG, "nx_merkle_leaf_chain: row range outside the column");
     if (n_rows == 0) return NX_OK;
     ColSet cs; NX_TRY(make_colset(ctx, d_cols, n_cols, &cs));
-    return leaf_chain_launch(ctx, ctx->stream, cs, n_cols, col_offset, total_cols, d_state_in, d_state_out, row_begin, n_rows);
+    return leaf_chain_launch(ctx, cs, n_cols, col_offset, total_cols, d_state_in, d_state_out, row_begin, n_rows);
 }
 
 int nx_merkle_from_leaves(nx_ctx* ctx, const uint32_t* d_leaf_digests, uint32_t log_size, nx_tree** out) {

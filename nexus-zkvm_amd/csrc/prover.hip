@@ -238,10 +238,8 @@ void plan_local_columns(const std::vector<std::pair<uint32_t, uint32_t>>& groups
 }
 
 // TreeBuilder::commit = CommitmentTreeProver::new (LDE of every polynomial) + MerkleProver::commit.  The leaf layer is one
-// Blake2s chain per row over the largest columns in commit order, so it is built incrementally: as soon as a group of
-// columns is extended, its 16-column blocks are absorbed on the hash stream while the main stream already extends the next
-// group (tree_pipe_* in merkle.hip).
-static uint32_t pipe_group_cols(const nx_ctx* ctx) { return ctx->opt.commit_pipe_cols >= 16 ? (uint32_t)ctx->opt.commit_pipe_cols : (1u << 30); }
+// Blake2s chain per row over the largest columns in commit order, so it is built incrementally: as soon as a run of columns is
+// extended, its 16-column blocks are absorbed, in stream order (tree_pipe_* in merkle.hip).
 
 int TreeBuilder::commit_end(Blake2sChannel& channel) {
     if (cs.dist.on()) return commit_dist(channel);
@@ -268,9 +266,8 @@ int TreeBuilder::commit_begin() {
     for (auto& g : groups) if (g.lo != 0 || g.hi != g.n_cols) return set_err(ctx, NX_ERR_ARG, "TreeBuilder: a column shard was handed to a single-GPU commitment scheme");
     TreePipe tp;
     struct PipeGuard { nx_ctx* c; TreePipe* p; ~PipeGuard() { if (p->tree) { (void)nx_sync(c); nx_tree_destroy(p->tree); p->tree = nullptr; } } } guard{ctx, &tp};
-    if (total_leaf_cols) { H_TRY(tree_pipe_begin(ctx, max_el, total_leaf_cols, &tp)); tp.side_stream = pipe_group_cols(ctx) < (1u << 29); }
+    if (total_leaf_cols) H_TRY(tree_pipe_begin(ctx, max_el, total_leaf_cols, &tp));
     std::vector<const uint32_t*> small_cols; std::vector<uint32_t> small_logs;
-    const uint32_t G = pipe_group_cols(ctx);
     // consecutive groups of one size (the components of a prover2-style statement) are extended by ONE batch call: a tree of 55 small
     // components is 6 calls, not 55 (each call forks/joins the FFT streams and is launch-bound below ~2^16 rows)
     for (size_t g0 = 0; g0 < groups.size();) {
@@ -309,8 +306,8 @@ int TreeBuilder::commit_begin() {
             HostFeed* feed = nullptr;
             if (any_host) { feeds.emplace_back(new HostFeed()); feed = feeds.back().get(); H_TRY(feed->begin(ctx, log, coset_order)); }
             // chunks of 16 columns when the run is fed from the host (a chunk's transforms start when IT has arrived; 16 columns of 2^22
-            // rows are 5 ms of PCIe and 0.7 ms of transforms), else the whole run (or NX_PIPE_COLS groups) per call
-            const uint32_t step = any_host ? 16u : (leaf ? G : n_run);
+            // rows are 5 ms of PCIe and 0.7 ms of transforms), else the whole run in one call
+            const uint32_t step = any_host ? 16u : n_run;
             for (uint32_t c0 = 0; c0 < n_run; c0 += step) {
                 const uint32_t nb = std::min(step, n_run - c0);
                 if (any_host) {

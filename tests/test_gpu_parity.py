@@ -102,6 +102,9 @@ def test_context_options_are_per_context_and_validated(nz):
         for name, v in (("fft.streams", 9), ("air.quarter_domain", 3), ("fft.pipe", 1), ("no.such.option", 1), ("air.segment", 1)):
             with pytest.raises(nz.NexusHipError):
                 a.set_option(name, v)
+        for name in ("commit.pipe_cols", "machine.queue_trees", "logup.staged"):   # retired with their code paths
+            with pytest.raises(nz.NexusHipError, match="unknown option"):
+                a.set_option(name, 0)
     finally:
         a.close(); b.close()
 
@@ -1266,11 +1269,11 @@ def test_logup_cols_batched_matches_oracle(be, oracle, log):
 
 
 @pytest.mark.parametrize("log", [6, 13])
-def test_logup_cols_staged_reads_equal_the_direct_ones_and_the_oracle(be, nz, oracle, log):
-    """nx_logup_cols requests every read of a group of 8 fractions up front and parks the values in LDS ("logup.staged", default on) when
-    the group's tuples are at most 32 columns wide, and reads where it uses them otherwise.  Groups of 21 columns (three request rounds),
-    of exactly 32, of 33 (the direct path) and a ragged last group of 3 fractions, with and without multiplicities, secure and base
-    numerators: staged == direct ("logup.staged" = 0) == the oracle's LogupColGenerator chain, every column."""
+def test_logup_cols_staged_and_wide_groups_equal_the_oracle(be, oracle, log):
+    """nx_logup_cols requests every read of a group of 8 fractions up front and parks the values in LDS when the group's tuples are at
+    most 32 columns wide, and reads where it uses them otherwise.  Groups of 21 columns (three request rounds), of exactly 32, of 33 (the
+    direct path) and a ragged last group of 3 fractions, with and without multiplicities, secure and base numerators: == the oracle's
+    LogupColGenerator chain, every column."""
     rng = np.random.default_rng(4100 + log)
     n = 1 << log
     widths = [3, 1, 2, 4, 1, 2, 3, 5,   4, 4, 4, 4, 4, 4, 4, 4,   5, 4, 4, 4, 4, 4, 4, 4,   8, 1, 2]
@@ -1287,22 +1290,18 @@ def test_logup_cols_staged_reads_equal_the_direct_ones_and_the_oracle(be, nz, or
     for f in range(F):
         prev = oracle.logup_finalize_col(oracle.logup_combine(list(tup[f]), ap[:widths[f]], z), scale_a=scale[f], mult_a=mult[f], prev=prev)
         want.append(np.stack(prev))
-    direct = nz.HipBackend(0)
-    direct.set_option("logup.staged", 0)
-    for b in (be, direct):
-        fracs = []
-        for f in range(F):
-            d = dict(tuple=b.columns_from_host(tup[f]), alphas=ap[:widths[f]], z=z, scale=scale[f])
-            if mult[f] is not None:
-                d["mult"] = b.columns_from_host(mult[f])
-            fracs.append(d)
-        got = b.logup_cols(fracs)
-        for f in range(F):
-            assert np.array_equal(got[f].to_cpu(), want[f]), (b is be, f)
-        pairs = b.logup_cols_batched(fracs)                        # pairs: the running sum after every second fraction (and after the odd last one)
-        for j, g in enumerate(pairs):
-            assert np.array_equal(g.to_cpu(), want[min(2 * j + 1, F - 1)]), (b is be, j)
-    direct.close()
+    fracs = []
+    for f in range(F):
+        d = dict(tuple=be.columns_from_host(tup[f]), alphas=ap[:widths[f]], z=z, scale=scale[f])
+        if mult[f] is not None:
+            d["mult"] = be.columns_from_host(mult[f])
+        fracs.append(d)
+    got = be.logup_cols(fracs)
+    for f in range(F):
+        assert np.array_equal(got[f].to_cpu(), want[f]), f
+    pairs = be.logup_cols_batched(fracs)                           # pairs: the running sum after every second fraction (and after the odd last one)
+    for j, g in enumerate(pairs):
+        assert np.array_equal(g.to_cpu(), want[min(2 * j + 1, F - 1)]), j
 
 
 @pytest.mark.parametrize("log,batching,segment", [(6, "pairs", 9000), (12, "single", 9000), (12, [2, 0, 1, 1, 0], 200), (15, "pairs", 300)])
