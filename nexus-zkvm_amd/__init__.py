@@ -333,17 +333,7 @@ class ProverSession:
     def commit_host(self, cols, coset_order=False, keep=()):
         """nx_prover_tree_commit_host: the tree's columns stay in HOST memory (numpy) and are uploaded chunk by chunk under the commit's
         own transforms.  keep: column indices whose evaluations are cloned on arrival; returns (root, {index: DeviceColumns})."""
-        cols = [_u32(c) for c in cols]
-        logs = [int(np.log2(len(c))) for c in cols]
-        self.tree_begin(logs)
-        hp = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data for c in cols])
-        kept = {int(k): DeviceColumns(self.be, 1, logs[int(k)]) for k in keep}
-        ki = _u32(list(kept.keys()))
-        kd = (C.c_void_p * max(1, len(kept)))(*[d.ptr.value for d in kept.values()])
-        root = np.zeros(8, np.uint32)
-        self.be._chk(self.be.L.nx_prover_tree_commit_host(self.h, hp, int(bool(coset_order)), ki.ctypes.data_as(C.c_void_p) if len(kept) else None, len(kept),
-                                                         kd if len(kept) else None, root.ctypes.data_as(C.c_void_p)))
-        return root, kept
+        return self._commit_host([_u32(c) for c in cols], None, coset_order, keep)
 
     def commit_host_narrow(self, cols, coset_order=False, keep=(), as_kind=None):
         """nx_prover_tree_commit_host_narrow: commit_host for host columns of uint8 / uint16 / uint32 arrays (the kind follows the dtype;
@@ -351,16 +341,20 @@ class ProverSession:
         widened on the device.  A value that does not fit its declared width raises; the tree is then no longer begun and the transcript
         is untouched.  Returns (root, {index: DeviceColumns})."""
         arrs, kinds = _narrow_columns(cols, as_kind)
+        return self._commit_host(arrs, kinds, coset_order, keep)
+
+    def _commit_host(self, arrs, kinds, coset_order, keep):
+        """commit_host (kinds None: nx_prover_tree_commit_host) and commit_host_narrow (nx_prover_tree_commit_host_narrow)."""
+        L = self.be.L
+        fn = L.nx_prover_tree_commit_host if kinds is None else L.nx_prover_tree_commit_host_narrow
         logs = [int(np.log2(len(c))) for c in arrs]
         self.tree_begin(logs)
-        hp = (C.c_void_p * max(1, len(arrs)))(*[c.ctypes.data for c in arrs])
         kept = {int(k): DeviceColumns(self.be, 1, logs[int(k)]) for k in keep}
         ki = _u32(list(kept.keys()))
         kd = (C.c_void_p * max(1, len(kept)))(*[d.ptr.value for d in kept.values()])
         root = np.zeros(8, np.uint32)
-        self.be._chk(self.be.L.nx_prover_tree_commit_host_narrow(self.h, hp, kinds.ctypes.data_as(C.c_void_p), int(bool(coset_order)),
-                                                                ki.ctypes.data_as(C.c_void_p) if len(kept) else None, len(kept),
-                                                                kd if len(kept) else None, root.ctypes.data_as(C.c_void_p)))
+        self.be._chk(fn(self.h, *_host_columns(arrs, kinds), int(bool(coset_order)), ki.ctypes.data_as(C.c_void_p) if len(kept) else None, len(kept),
+                        kd if len(kept) else None, root.ctypes.data_as(C.c_void_p)))
         return root, kept
 
     def share_tree(self, tree_index):
@@ -526,6 +520,13 @@ def _narrow_columns(cols, as_kind=None):
         w = _as_width(spec)
         kinds.append(COL_U32 if w is None else COL_U32_AS_U8 if w == 1 else COL_U32_AS_U16)
     return arrs, np.array(kinds, dtype=np.uint8)
+
+
+def _host_columns(arrs, kinds):
+    """The arguments a host-column entry point takes for its columns: the pointer table of `arrs` and — for the narrow form (kinds not
+    None) — their NX_COL_* kinds right behind it."""
+    hp = (C.c_void_p * max(1, len(arrs)))(*[c.ctypes.data for c in arrs])
+    return (hp,) if kinds is None else (hp, kinds.ctypes.data_as(C.c_void_p))
 
 
 def default_config(pow_bits=10, log_blowup=1, n_queries=3, log_last_layer_degree_bound=0, hash_mode=HASH_BLAKE2S,
@@ -732,22 +733,21 @@ class HipBackend:
         """A whole host trace (list of 1-D uint32 arrays of one size) -> DeviceColumns, pinned in place and streamed
         (nx_upload_columns); coset_order: the host holds natural coset order (reference trace builders) and wants the
         bit-reversed circle-domain order on device."""
-        cols = [_u32(c) for c in host_cols]
-        log = int(np.log2(cols[0].size))
-        out = DeviceColumns(self, len(cols), log)
-        hp = (C.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
-        self._chk(self.L.nx_upload_columns(self.ctx, hp, len(cols), log, out.col_ptrs(), 1 if coset_order else 0))
-        return out
+        return self._upload_columns([_u32(c) for c in host_cols], None, coset_order)
 
     def upload_columns_narrow(self, host_cols, coset_order=True, as_kind=None):
         """nx_upload_columns_narrow: upload_columns for host columns of uint8 / uint16 / uint32 arrays of one size (the kind follows the
         dtype; as_kind declares uint32 columns to hold byte or half-word values).  Narrow columns cross PCIe narrow and are widened on
         the device; a value that does not fit its declared width raises NexusHipError.  -> DeviceColumns of u32 words."""
         arrs, kinds = _narrow_columns(host_cols, as_kind)
+        return self._upload_columns(arrs, kinds, coset_order)
+
+    def _upload_columns(self, arrs, kinds, coset_order):
+        """upload_columns (kinds None: nx_upload_columns) and upload_columns_narrow (nx_upload_columns_narrow)."""
+        fn = self.L.nx_upload_columns if kinds is None else self.L.nx_upload_columns_narrow
         log = int(np.log2(arrs[0].size))
         out = DeviceColumns(self, len(arrs), log)
-        hp = (C.c_void_p * len(arrs))(*[c.ctypes.data for c in arrs])
-        self._chk(self.L.nx_upload_columns_narrow(self.ctx, hp, kinds.ctypes.data_as(C.c_void_p), len(arrs), log, out.col_ptrs(), 1 if coset_order else 0))
+        self._chk(fn(self.ctx, *_host_columns(arrs, kinds), len(arrs), log, out.col_ptrs(), 1 if coset_order else 0))
         return out
 
     def host_pin(self, arr):
@@ -1110,35 +1110,25 @@ class HipBackend:
     def prove_machine_host(self, comps, cfg, pre_cols, main_cols, ad=b"", coset_order=False, want_stats=False):
         """nx_prove_machine_host: the machine's preprocessed / main traces from HOST memory (lists of contiguous uint32 arrays, component
         after component), uploaded under the commits' own transforms.  Same proof as prove_machine for the same trace."""
-        cfg = cfg or default_config()
-        keep = [np.ascontiguousarray(c, dtype=np.uint32) for c in list(pre_cols) + list(main_cols)]
-        n_pre = len(pre_cols)
-        pp = (C.c_void_p * max(1, n_pre))(*[c.ctypes.data for c in keep[:n_pre]])
-        mp = (C.c_void_p * max(1, len(keep) - n_pre))(*[c.ctypes.data for c in keep[n_pre:]])
-        words, n = C.POINTER(C.c_uint32)(), C.c_size_t(0)
-        stats = ProveStats()
-        adb = (C.c_uint8 * max(1, len(ad)))(*ad)
-        self._chk(self.L.nx_prove_machine_host(self.ctx, self._comps(comps), len(comps), C.byref(cfg), pp, mp, int(bool(coset_order)), adb, C.c_size_t(len(ad)),
-                                               C.byref(words), C.byref(n), C.byref(stats) if want_stats else None))
-        out = np.ctypeslib.as_array(words, shape=(n.value,)).copy()
-        self.L.nx_free_host(words)
-        return (out, stats.as_dict()) if want_stats else out
+        return self._prove_machine_host(comps, cfg, [_u32(c) for c in pre_cols], None, [_u32(c) for c in main_cols], None, ad, coset_order, want_stats)
 
     def prove_machine_host_narrow(self, comps, cfg, pre_cols, main_cols, ad=b"", coset_order=False, want_stats=False, pre_as=None, main_as=None):
         """nx_prove_machine_host_narrow: prove_machine_host with host columns of uint8 / uint16 / uint32 arrays (the kind follows the
         dtype; pre_as / main_as declare uint32 columns to hold byte or half-word values, as as_kind of upload_columns_narrow).  Same proof
         as prove_machine_host for the same values; a value that does not fit its declared width raises NexusHipError."""
-        cfg = cfg or default_config()
         pre, pk = _narrow_columns(pre_cols, pre_as)
         main, mk = _narrow_columns(main_cols, main_as)
-        pp = (C.c_void_p * max(1, len(pre)))(*[c.ctypes.data for c in pre])
-        mp = (C.c_void_p * max(1, len(main)))(*[c.ctypes.data for c in main])
+        return self._prove_machine_host(comps, cfg, pre, pk, main, mk, ad, coset_order, want_stats)
+
+    def _prove_machine_host(self, comps, cfg, pre, pre_kinds, main, main_kinds, ad, coset_order, want_stats):
+        """prove_machine_host (kinds None: nx_prove_machine_host) and prove_machine_host_narrow (nx_prove_machine_host_narrow)."""
+        fn = self.L.nx_prove_machine_host if pre_kinds is None else self.L.nx_prove_machine_host_narrow
+        cfg = cfg or default_config()
         words, n = C.POINTER(C.c_uint32)(), C.c_size_t(0)
         stats = ProveStats()
         adb = (C.c_uint8 * max(1, len(ad)))(*ad)
-        self._chk(self.L.nx_prove_machine_host_narrow(self.ctx, self._comps(comps), len(comps), C.byref(cfg), pp, pk.ctypes.data_as(C.c_void_p), mp,
-                                                      mk.ctypes.data_as(C.c_void_p), int(bool(coset_order)), adb, C.c_size_t(len(ad)),
-                                                      C.byref(words), C.byref(n), C.byref(stats) if want_stats else None))
+        self._chk(fn(self.ctx, self._comps(comps), len(comps), C.byref(cfg), *_host_columns(pre, pre_kinds), *_host_columns(main, main_kinds),
+                     int(bool(coset_order)), adb, C.c_size_t(len(ad)), C.byref(words), C.byref(n), C.byref(stats) if want_stats else None))
         out = np.ctypeslib.as_array(words, shape=(n.value,)).copy()
         self.L.nx_free_host(words)
         return (out, stats.as_dict()) if want_stats else out

@@ -602,60 +602,6 @@ int nx_finalize_columns(nx_ctx* ctx, const uint32_t* const* d_src_natural, uint3
     return NX_OK;
 }
 
-
-// R3 + R4 for a whole host-resident trace: pin every host column in place (hipHostRegister, no
-// staging copy), stream it over PCIe on a side stream and run the coset-order -> bit-reversed-circle-domain permutation
-// (or nothing, when the host already holds that order) behind it on the main stream, two columns in flight.  This replaces
-// the reference's per-column CPU passes (coset_order_to_circle_domain_order + from_iter + bit_reverse_column + clone).
-int nx_upload_columns(nx_ctx* ctx, const uint32_t* const* h_cols, uint32_t n_cols, uint32_t log_size, uint32_t* const* d_cols, int coset_order) {
-    NX_GUARD(ctx);
-    if (!ctx || (n_cols && (!h_cols || !d_cols))) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns: NULL argument");
-    if (log_size < 1 || log_size > 30) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns: bad log_size");
-    const size_t n = (size_t)1 << log_size, bytes = n * 4;
-    uint32_t* d_tmp[2] = {nullptr, nullptr};
-    hipEvent_t copied[2], consumed[2];
-    int rc = NX_OK;
-    if (coset_order) for (int k = 0; k < 2 && rc == NX_OK; k++) rc = dev_alloc(ctx, bytes, (void**)&d_tmp[k]);
-    for (int k = 0; k < 2; k++) { (void)hipEventCreateWithFlags(&copied[k], hipEventDisableTiming); (void)hipEventCreateWithFlags(&consumed[k], hipEventDisableTiming); }
-    hipStream_t copy_stream = ctx->side[0];
-    hipError_t e = hipEventRecord(ctx->fork_ev, ctx->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(copy_stream, ctx->fork_ev, 0);
-    std::vector<bool> registered(n_cols, false);
-    for (uint32_t c = 0; c < n_cols && rc == NX_OK && e == hipSuccess; c++) {
-        const int k = c & 1;
-        registered[c] = !host_pinned_by_owner(h_cols[c], bytes) && hipHostRegister((void*)h_cols[c], bytes, hipHostRegisterDefault) == hipSuccess;   // else pinned by its owner, or a pageable copy
-        if (!registered[c]) (void)hipGetLastError();
-        uint32_t* dst = coset_order ? d_tmp[k] : d_cols[c];
-        if (coset_order && c >= 2) e = hipStreamWaitEvent(copy_stream, consumed[k], 0);      // the permute kernel of column c-2 has read d_tmp[k]
-        if (e == hipSuccess) {
-            // a column that could not be pinned (already registered by someone else, ...) goes through the context's bounce buffer: a
-            // straight copy from pageable memory would be pinned in place by the runtime and released lazily (internal.h, h_bounce)
-            if (registered[c] || host_pinned_by_owner(h_cols[c], bytes)) e = hipMemcpyAsync(dst, h_cols[c], bytes, hipMemcpyHostToDevice, copy_stream);
-            else if (copy_h2d_blocking(ctx, dst, h_cols[c], bytes, copy_stream) != NX_OK) e = hipErrorUnknown;
-        }
-        if (e == hipSuccess) e = hipEventRecord(copied[k], copy_stream);
-        if (e == hipSuccess && coset_order) {
-            e = hipStreamWaitEvent(ctx->stream, copied[k], 0);
-            if (e == hipSuccess) {
-                ColSet s1, d1; s1.base = d_tmp[k]; s1.stride = 0; s1.table = nullptr; d1.base = d_cols[c]; d1.stride = 0; d1.table = nullptr;
-                hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + 255) / 256), 1), dim3(256), 0, ctx->stream, s1, d1, 1u, (int)log_size);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipEventRecord(consumed[k], ctx->stream);
-        }
-    }
-    // the caller may reuse / free the host columns on return: everything must have left them
-    hipError_t e2 = hipStreamSynchronize(copy_stream);
-    hipError_t e3 = hipStreamSynchronize(ctx->stream);
-    for (uint32_t c = 0; c < n_cols; c++) if (registered[c]) (void)hipHostUnregister((void*)h_cols[c]);
-    for (int k = 0; k < 2; k++) { (void)hipEventDestroy(copied[k]); (void)hipEventDestroy(consumed[k]); dev_free(ctx, d_tmp[k]); }
-    if (rc != NX_OK) return rc;
-    if (e != hipSuccess) return hip_fail(ctx, e, "nx_upload_columns", __FILE__, __LINE__);
-    if (e2 != hipSuccess) return hip_fail(ctx, e2, "nx_upload_columns(copy sync)", __FILE__, __LINE__);
-    if (e3 != hipSuccess) return hip_fail(ctx, e3, "nx_upload_columns(sync)", __FILE__, __LINE__);
-    return NX_OK;
-}
-
 }  // extern "C" (re-opened below)
 namespace nx {
 int HostFeed::begin(nx_ctx* c, uint32_t log_size, int coset) {
@@ -742,29 +688,32 @@ int HostFeed::chunk(const void* const* h_cols, const uint8_t* kinds, const uint3
             n_packed++;
         }
     }
-    // 2. the copies (and, for narrow columns, the widening behind them)
+    // 2. the copies (and, for narrow columns, the widening behind them).  Column c is copied straight from host memory that is pinned —
+    //    by its owner (nx_host_pin), by this feed until finish(), or the staging ring it was packed into —; memory that cannot be pinned
+    //    goes through the context's bounce buffer (never a pin-in-place copy: internal.h, h_bounce)
+    auto h2d = [&](void* dst, uint32_t c, hipStream_t st) -> int {
+        const size_t nb = n * kind_width(kind_of(c));
+        const void* src = narrow_src[c] ? narrow_src[c] : h_cols[c];
+        if (!narrow_src[c] && !host_pinned_by_owner(src, nb)) {
+            if (hipHostRegister((void*)src, nb, hipHostRegisterDefault) != hipSuccess) { (void)hipGetLastError(); return copy_h2d_blocking(ctx, dst, src, nb, st); }
+            pinned.push_back(src);
+        }
+        NX_HIP(ctx, hipMemcpyAsync(dst, src, nb, hipMemcpyHostToDevice, st));
+        return NX_OK;
+    };
     bool any_narrow = false;
     for (uint32_t c = 0; c < n_cols; c++) {
         if (!h_cols[c] || !d_cols[c]) return set_err(ctx, NX_ERR_ARG, "host feed: NULL column");
         const uint8_t kind = kind_of(c);
         if (kind == NX_COL_U32) {
-            const uint32_t* h = (const uint32_t*)h_cols[c];
-            bool dma_ok = true;
-            if (host_pinned_by_owner(h, bytes)) {}                      // pinned once by its owner (nx_host_pin)
-            else if (hipHostRegister((void*)h, bytes, hipHostRegisterDefault) == hipSuccess) pinned.push_back(h);
-            else { (void)hipGetLastError(); dma_ok = false; }                         // not pinnable: through the bounce buffer (never a pin-in-place copy: internal.h, h_bounce)
             const int k = (int)(n_slot & 1);
-            auto h2d = [&](uint32_t* dst, hipStream_t st) -> int {
-                if (dma_ok) { NX_HIP(ctx, hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, st)); return NX_OK; }
-                return copy_h2d_blocking(ctx, dst, h, bytes, st);
-            };
             if (!coset_order) {
                 // no permutation to run: the second stream carries every other column's copy (two DMA queues in flight: 136.6 -> 132.7 ms
                 // for the 374-column headline trace, bench.py host_trace)
-                NX_TRY(h2d(d_cols[c], (n_done & 1) ? ctx->perm_stream : ctx->copy_stream));
+                NX_TRY(h2d(d_cols[c], c, (n_done & 1) ? ctx->perm_stream : ctx->copy_stream));
             } else {
                 if (n_slot >= 2) NX_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, consumed[k], 0));      // the permutation of column n_slot - 2 has read d_tmp[k]
-                NX_TRY(h2d(d_tmp[k], ctx->copy_stream));
+                NX_TRY(h2d(d_tmp[k], c, ctx->copy_stream));
                 NX_HIP(ctx, hipEventRecord(copied[k], ctx->copy_stream));
                 NX_HIP(ctx, hipStreamWaitEvent(ctx->perm_stream, copied[k], 0));
                 ColSet s1, d1; s1.base = d_tmp[k]; s1.stride = 0; s1.table = nullptr; d1.base = d_cols[c]; d1.stride = 0; d1.table = nullptr;
@@ -780,15 +729,6 @@ int HostFeed::chunk(const void* const* h_cols, const uint8_t* kinds, const uint3
         // slot, as the u32 !coset_order copies alternate: two DMA queues in flight)
         any_narrow = true;
         const int w = kind_width(kind);
-        const size_t nb = n * w;
-        const void* src = narrow_src[c];
-        bool dma_ok = true;
-        if (!src) {
-            src = h_cols[c];
-            if (host_pinned_by_owner(src, nb)) {}
-            else if (hipHostRegister((void*)src, nb, hipHostRegisterDefault) == hipSuccess) pinned.push_back(src);
-            else { (void)hipGetLastError(); dma_ok = false; }
-        }
         const int k = (int)(n_slot & 1);
         hipStream_t st = k ? ctx->perm_stream : ctx->copy_stream;
         if (!d_tmp[k]) {
@@ -802,8 +742,7 @@ int HostFeed::chunk(const void* const* h_cols, const uint8_t* kinds, const uint3
             NX_HIP(ctx, hipStreamWaitEvent(ctx->perm_stream, here, 0));
         }
         if (n_slot >= 2) NX_HIP(ctx, hipStreamWaitEvent(st, consumed[k], 0));      // the column of slot k before this one has been read
-        if (dma_ok) NX_HIP(ctx, hipMemcpyAsync(d_tmp[k], src, nb, hipMemcpyHostToDevice, st));
-        else NX_TRY(copy_h2d_blocking(ctx, d_tmp[k], src, nb, st));
+        NX_TRY(h2d(d_tmp[k], c, st));
         const uint8_t* s8 = (const uint8_t*)d_tmp[k];
         // every runtime call above was checked by its return code; the launch check below must see this launch's status only (the pin
         // attempts of narrow columns leave a stale "not registered" status behind them: HIP error 713 on MI355X)
@@ -859,11 +798,20 @@ int HostFeed::finish() {
     if (e2 != hipSuccess) return hip_fail(c, e2, "host feed (permutation stream)", __FILE__, __LINE__);
     return NX_OK;
 }
-}  // namespace nx
-extern "C" {
-
-}  // extern "C" (re-opened below)
-namespace nx {
+int upload_columns(nx_ctx* ctx, const void* const* h_cols, const uint8_t* kinds, uint32_t n_cols, uint32_t log_size, uint32_t* const* d_cols,
+                   int coset_order, const uint32_t* call_col, const char* what) {
+    for (uint32_t c = 0; c < n_cols; c++) {
+        if (kinds && kinds[c] > NX_COL_U32_AS_U8) return set_err(ctx, NX_ERR_ARG, std::string(what) + ": unknown column kind");
+        if (!h_cols[c] || !d_cols[c]) return set_err(ctx, NX_ERR_ARG, std::string(what) + ": NULL column");
+    }
+    HostFeed feed;                                           // finish() on every path: the host columns are the caller's again on return
+    NX_TRY(feed.begin(ctx, log_size, coset_order));
+    for (uint32_t c0 = 0; c0 < n_cols; c0 += 16) {           // 16-column chunks: the pack of one runs while the previous one is on the bus
+        hipEvent_t ready = nullptr;
+        NX_TRY(feed.chunk(h_cols + c0, kinds ? kinds + c0 : nullptr, call_col ? call_col + c0 : nullptr, what, d_cols + c0, std::min(16u, n_cols - c0), &ready));
+    }
+    return feed.finish();
+}
 // (the runtime accepts a second registration of a range, and the first hipHostUnregister then drops both: the book is kept here,
 // process-wide because the registration is)
 struct PinBook { std::mutex mu; std::map<const uint8_t*, size_t> ranges; };
@@ -906,50 +854,31 @@ int nx_host_unpin(nx_ctx* ctx, const void* h) {
     return NX_OK;
 }
 
+// R3 + R4 for a whole host-resident trace: the all-NX_COL_U32 case of nx_upload_columns_narrow.  This replaces
+// the reference's per-column CPU passes (coset_order_to_circle_domain_order + from_iter + bit_reverse_column + clone).
+int nx_upload_columns(nx_ctx* ctx, const uint32_t* const* h_cols, uint32_t n_cols, uint32_t log_size, uint32_t* const* d_cols, int coset_order) {
+    NX_GUARD(ctx);
+    if (!ctx || (n_cols && (!h_cols || !d_cols))) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns: NULL argument");
+    if (log_size < 1 || log_size > 30) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns: bad log_size");
+    return upload_columns(ctx, (const void* const*)h_cols, nullptr, n_cols, log_size, d_cols, coset_order, nullptr, "nx_upload_columns: h_cols");
+}
+
 int nx_upload_columns_narrow(nx_ctx* ctx, const void* const* h_cols, const uint8_t* kinds, uint32_t n_cols, uint32_t log_size, uint32_t* const* d_cols,
                              int coset_order) {
     NX_GUARD(ctx);
     if (!ctx || !h_cols || !d_cols || !n_cols) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns_narrow: NULL argument or no columns");
+    if (log_size < 1 || log_size > 30) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns_narrow: bad log_size");
     std::vector<uint32_t> idx(n_cols);
     for (uint32_t c = 0; c < n_cols; c++) idx[c] = c;
-    return upload_columns_narrow(ctx, h_cols, kinds, n_cols, log_size, d_cols, coset_order, idx.data(), "nx_upload_columns_narrow: h_cols");
+    return upload_columns(ctx, h_cols, kinds, n_cols, log_size, d_cols, coset_order, idx.data(), "nx_upload_columns_narrow: h_cols");
 }
-
-}  // extern "C" (re-opened below)
-namespace nx {
-int upload_columns_narrow(nx_ctx* ctx, const void* const* h_cols, const uint8_t* kinds, uint32_t n_cols, uint32_t log_size, uint32_t* const* d_cols,
-                          int coset_order, const uint32_t* call_col, const char* what) {
-    bool any_narrow = false;
-    for (uint32_t c = 0; c < n_cols && kinds; c++) {
-        if (kinds[c] > NX_COL_U32_AS_U8) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns_narrow: unknown column kind");
-        any_narrow |= kinds[c] != NX_COL_U32;
-    }
-    if (!any_narrow) return nx_upload_columns(ctx, (const uint32_t* const*)h_cols, n_cols, log_size, d_cols, coset_order);
-    if (log_size < 1 || log_size > 30) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns_narrow: bad log_size");
-    for (uint32_t c = 0; c < n_cols; c++) if (!h_cols[c] || !d_cols[c]) return set_err(ctx, NX_ERR_ARG, "nx_upload_columns_narrow: NULL column");
-    HostFeed feed;                                           // finish() on every path: the host columns are the caller's again on return
-    NX_TRY(feed.begin(ctx, log_size, coset_order));
-    for (uint32_t c0 = 0; c0 < n_cols; c0 += 16) {           // 16-column chunks: the pack of one runs while the previous one is on the bus
-        hipEvent_t ready = nullptr;
-        NX_TRY(feed.chunk(h_cols + c0, kinds + c0, call_col + c0, what, d_cols + c0, std::min(16u, n_cols - c0), &ready));
-    }
-    return feed.finish();
-}
-}  // namespace nx
-extern "C" {
 
 int nx_upload_coset_order(nx_ctx* ctx, const uint32_t* h_natural, uint32_t log_size, uint32_t* d_dst) {
     NX_GUARD(ctx);
     if (!ctx || !h_natural || !d_dst) return set_err(ctx, NX_ERR_ARG, "nx_upload_coset_order: NULL argument");
     if (log_size < 1 || log_size > 30) return set_err(ctx, NX_ERR_ARG, "nx_upload_coset_order: bad log_size");
-    uint32_t* d_tmp = nullptr;
-    size_t n = (size_t)1 << log_size;
-    NX_TRY(dev_alloc(ctx, n * 4, (void**)&d_tmp));
-    int rc = copy_h2d_blocking(ctx, d_tmp, h_natural, n * 4);
-    if (rc == NX_OK) { const uint32_t* sp = d_tmp; uint32_t* dp = d_dst; rc = nx_finalize_columns(ctx, &sp, &dp, 1, log_size); }
-    (void)hipStreamSynchronize(ctx->stream);
-    dev_free(ctx, d_tmp);
-    return rc;
+    const void* h = h_natural;
+    return upload_columns(ctx, &h, nullptr, 1, log_size, &d_dst, 1, nullptr, "nx_upload_coset_order: h_natural");
 }
 
 }  // extern "C"

@@ -226,22 +226,24 @@ int copy_h2d_blocking(nx_ctx* ctx, void* d_dst, const void* h_src, size_t bytes,
 int copy_d2h_blocking(nx_ctx* ctx, void* h_dst, const void* d_src, size_t bytes);
 // stream-ordered upload of caller host memory that may be freed as soon as this returns (through the staging ring, in chunks)
 int upload_async_staged(nx_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
-// Narrow columns (kinds != null, NX_COL_* of include/nexus_hip.h): an NX_COL_U16 / NX_COL_U8 column is pinned at its real byte length,
-// copied into a d_tmp slot and widened by widen_kernel on perm_stream; an NX_COL_U32_AS_* column is packed (and checked) on host
-// threads into the context's staging ring first (h_pack), then copied and widened the same way.  The chunk's packing ends before any of
-// its copies is queued, so a refused chunk is never sent.  call_col: index of each column in the caller's array (the refusal names it);
-// what: the caller's name of that array.  An NX_COL_U32 column takes the u32 path unchanged.
+// Column kinds (kinds: NX_COL_* of include/nexus_hip.h, null = all NX_COL_U32): an NX_COL_U32 column is copied as it is, into its
+// destination (circle order; alternating copy_stream and perm_stream) or into a d_tmp slot ahead of the permutation (coset order); an
+// NX_COL_U16 / NX_COL_U8 column is pinned at its real byte length, copied into a d_tmp slot and widened by widen_kernel behind the copy,
+// both on one alternating queue; an NX_COL_U32_AS_* column is packed (and checked) on host threads into the context's staging ring
+// first (h_pack), then copied and widened the same way.  The chunk's packing ends before any of its copies is queued, so a refused chunk
+// is never sent.  call_col: index of each column in the caller's array (the refusal names it; null = the chunk's own index); what: the
+// caller's name of that array.
 void pack_ring_release(nx_ctx* ctx);
-// nx_upload_columns_narrow with the caller's column indices (call_col) and array name (what) for the refusal's message
-int upload_columns_narrow(nx_ctx* ctx, const void* const* h_cols, const uint8_t* kinds, uint32_t n_cols, uint32_t log_size, uint32_t* const* d_cols,
-                          int coset_order, const uint32_t* call_col, const char* what);
+// The one upload of host columns behind every entry point (nx_upload_columns*, nx_upload_coset_order, a row-sharded host commit): a
+// HostFeed run in 16-column chunks, blocking — the host columns are the caller's again on return.  kinds and call_col may be null.
+int upload_columns(nx_ctx* ctx, const void* const* h_cols, const uint8_t* kinds, uint32_t n_cols, uint32_t log_size, uint32_t* const* d_cols,
+                   int coset_order, const uint32_t* call_col, const char* what);
 struct HostFeed {
     nx_ctx* ctx = nullptr; int coset_order = 0; uint32_t log = 0;
     uint32_t* d_tmp[2] = {nullptr, nullptr}; hipEvent_t copied[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
     uint64_t n_done = 0, n_slot = 0, n_packed = 0;      // columns fed / through a d_tmp slot / chunks packed into the staging ring
     std::vector<const void*> pinned; std::vector<hipEvent_t> events;
     int begin(nx_ctx* c, uint32_t log_size, int coset);
-    int chunk(const uint32_t* const* h_cols, uint32_t* const* d_cols, uint32_t n_cols, hipEvent_t* ready) { return chunk((const void* const*)h_cols, nullptr, nullptr, nullptr, d_cols, n_cols, ready); }
     int chunk(const void* const* h_cols, const uint8_t* kinds, const uint32_t* call_col, const char* what, uint32_t* const* d_cols, uint32_t n_cols, hipEvent_t* ready);
     int finish();
     ~HostFeed() { (void)finish(); }

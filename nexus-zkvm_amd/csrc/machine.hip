@@ -664,9 +664,8 @@ static int prove_machine(nx_ctx* ctx, const nx_component_spec* comps, uint32_t n
                 }
                 const uint32_t col0 = tree == 0 ? locs[i].pre0 : locs[i].main0;
                 const uint8_t* kinds = tree == 0 ? host->pre_kinds : host->main_kinds;
-                if (kinds) tb.extend_evals_host(std::move(slab), n_tree, log, (tree == 0 ? host->pre : host->main) + col0, kinds + col0, host->coset_order, keep, col0,
-                                                tree == 0 ? "nx_prove_machine_host_narrow: h_pre_cols (preprocessed trace)" : "nx_prove_machine_host_narrow: h_main_cols (main trace)");
-                else tb.extend_evals_host(std::move(slab), n_tree, log, (const uint32_t* const*)(tree == 0 ? host->pre : host->main) + col0, host->coset_order, keep);
+                tb.extend_evals_host(std::move(slab), n_tree, log, (tree == 0 ? host->pre : host->main) + col0, kinds ? kinds + col0 : nullptr, host->coset_order, keep, col0,
+                                     tree == 0 ? "nx_prove_machine_host_narrow: h_pre_cols (preprocessed trace)" : "nx_prove_machine_host_narrow: h_main_cols (main trace)");
                 continue;
             }
             if (!need.empty()) {

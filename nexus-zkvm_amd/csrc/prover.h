@@ -161,9 +161,9 @@ class TreeBuilder {
     struct Group {
         DevBuf slab; uint32_t n_cols, log; bool is_evals; uint32_t lo, hi;   // slab: columns [lo, hi) of the group's n_cols (all of them on one GPU)
         // host-resident source (extend_evals_host): the slab is FILLED by the commit, from these host columns, while it transforms
-        std::vector<const uint32_t*> host; int coset_order = 0;
-        // narrow upload (NX_COL_*, empty = all NX_COL_U32): the element kind of each host column, its index in the caller's array (a refusal
-        // names it) and the caller's name of that array
+        std::vector<const void*> host; int coset_order = 0;
+        // the element kind of each host column (NX_COL_*, empty = all NX_COL_U32), its index in the caller's array (a refusal names it) and
+        // the caller's name of that array
         std::vector<uint8_t> kinds; uint32_t call_col0 = 0; const char* what = nullptr;
         std::vector<std::pair<uint32_t, uint32_t*>> keep;                    // (column of the group, device buffer): its evaluations, cloned before the transform (R4)
     };
@@ -172,20 +172,17 @@ class TreeBuilder {
     void extend_evals(DevBuf&& slab, uint32_t n_cols, uint32_t log) { push(std::move(slab), n_cols, log, true, 0, n_cols); }
     // The trace is in HOST memory (what the reference's trace builder hands over, prover/src/trace/trace_builder.rs:19-32): commit()
     // uploads it in column chunks on the copy stream — pinned in place, R3's permutation on the device when coset_order — and runs each
-    // chunk's iFFT + LDE as soon as the chunk has arrived, so the PCIe transfer and the transforms overlap (one GPU).  keep: columns whose
-    // evaluations are needed after the commit (the logup fractions read them): cloned on arrival, the reference's trace clone (machine.rs:232)
-    void extend_evals_host(DevBuf&& slab, uint32_t n_cols, uint32_t log, const uint32_t* const* h_cols, int coset_order,
-                           const std::vector<std::pair<uint32_t, uint32_t*>>& keep = {}) {
-        push(std::move(slab), n_cols, log, true, 0, n_cols);
-        groups.back().host.assign(h_cols, h_cols + n_cols); groups.back().coset_order = coset_order; groups.back().keep = keep;
-    }
-    // the same with an element kind per host column (NX_COL_*, kinds may be null = all NX_COL_U32; nx::HostFeed::chunk); call_col0 / what:
-    // where the group's columns start in the caller's array and its name, for the refusal's message
+    // chunk's iFFT + LDE as soon as the chunk has arrived, so the PCIe transfer and the transforms overlap (one GPU).  kinds: the element
+    // kind of each host column (NX_COL_*, null = all NX_COL_U32; nx::HostFeed::chunk).  keep: columns whose evaluations are needed after the
+    // commit (the logup fractions read them): cloned on arrival, the reference's trace clone (machine.rs:232).  call_col0 / what: where the
+    // group's columns start in the caller's array and its name, for the refusal's message
     void extend_evals_host(DevBuf&& slab, uint32_t n_cols, uint32_t log, const void* const* h_cols, const uint8_t* kinds, int coset_order,
                            const std::vector<std::pair<uint32_t, uint32_t*>>& keep, uint32_t call_col0, const char* what) {
-        extend_evals_host(std::move(slab), n_cols, log, (const uint32_t* const*)h_cols, coset_order, keep);
-        if (kinds) groups.back().kinds.assign(kinds, kinds + n_cols);
-        groups.back().call_col0 = call_col0; groups.back().what = what;
+        push(std::move(slab), n_cols, log, true, 0, n_cols);
+        Group& g = groups.back();
+        g.host.assign(h_cols, h_cols + n_cols); g.coset_order = coset_order; g.keep = keep;
+        if (kinds) g.kinds.assign(kinds, kinds + n_cols);
+        g.call_col0 = call_col0; g.what = what;
     }
     // row-sharded prove: the slab holds this GPU's columns [lo, hi) of the group (plan_local_columns)
     void extend_evals_local(DevBuf&& slab, uint32_t n_cols, uint32_t log, uint32_t lo, uint32_t hi) { push(std::move(slab), n_cols, log, true, lo, hi); }

@@ -285,9 +285,9 @@ int TreeBuilder::commit_begin() {
             auto out = col_ptrs(lde.p, n_run, el);
             const bool leaf = el == max_el;
             // host-resident columns of this run: per column its host source, and what to clone on arrival
-            std::vector<const uint32_t*> hsrc(n_run, nullptr); std::vector<uint32_t*> keep_of(n_run, nullptr);
+            std::vector<const void*> hsrc(n_run, nullptr); std::vector<uint32_t*> keep_of(n_run, nullptr);
             std::vector<uint8_t> hkind(n_run, (uint8_t)NX_COL_U32); std::vector<uint32_t> hcall(n_run, 0);
-            bool any_host = false, any_kind = false; int coset_order = 0; const char* what = nullptr;
+            bool any_host = false; int coset_order = 0; const char* what = nullptr;
             {
                 uint32_t off = 0;
                 for (size_t g = g0; g < g1; g++) {
@@ -296,7 +296,7 @@ int TreeBuilder::commit_begin() {
                         any_host = true; coset_order = groups[g].coset_order;
                         for (uint32_t k = 0; k < groups[g].n_cols; k++) hsrc[off + k] = groups[g].host[k];
                         for (uint32_t k = 0; k < groups[g].n_cols; k++) hcall[off + k] = groups[g].call_col0 + k;
-                        if (!groups[g].kinds.empty()) { any_kind = true; std::copy(groups[g].kinds.begin(), groups[g].kinds.end(), hkind.begin() + off); }
+                        if (!groups[g].kinds.empty()) std::copy(groups[g].kinds.begin(), groups[g].kinds.end(), hkind.begin() + off);
                         if (groups[g].what) what = groups[g].what;
                         for (auto& kv : groups[g].keep) { if (kv.first >= groups[g].n_cols) return set_err(ctx, NX_ERR_ARG, "TreeBuilder: keep index outside the group"); keep_of[off + kv.first] = kv.second; }
                     }
@@ -316,8 +316,7 @@ int TreeBuilder::commit_begin() {
                         if (!hsrc[a]) { a++; continue; }
                         uint32_t b2 = a; while (b2 < c0 + nb && hsrc[b2]) b2++;
                         hipEvent_t ready = nullptr;
-                        if (any_kind) H_TRY(feed->chunk((const void* const*)hsrc.data() + a, hkind.data() + a, hcall.data() + a, what, in.data() + a, b2 - a, &ready));
-                        else H_TRY(feed->chunk(hsrc.data() + a, in.data() + a, b2 - a, &ready));
+                        H_TRY(feed->chunk(hsrc.data() + a, hkind.data() + a, hcall.data() + a, what, in.data() + a, b2 - a, &ready));
                         NX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ready, 0));
                         a = b2;
                     }
@@ -1998,7 +1997,7 @@ int nx_committed_tree_root(const nx_committed_tree* t, uint8_t root[32], uint32_
 }
 
 }  // extern "C" (re-opened below)
-// nx_prover_tree_commit_host and its narrow form: kinds == nullptr is the u32 entry point, unchanged (nx_upload_columns / the u32 feed)
+// nx_prover_tree_commit_host and its narrow form (kinds == nullptr: all NX_COL_U32)
 static int tree_commit_host(nx_prover* p, const void* const* h_cols, const uint8_t* kinds, int coset_order, const uint32_t* keep_idx, uint32_t n_keep,
                             uint32_t* const* d_keep, uint8_t root[32], const char* fn) {
     NX_GUARD(p ? p->ctx : nullptr);
@@ -2018,17 +2017,13 @@ static int tree_commit_host(nx_prover* p, const void* const* h_cols, const uint8
         for (auto& r : p->pending) {
             if (sharded) {
                 // this GPU's columns of the run, uploaded before the commit (the exchange-bound sharded commit gains nothing from the overlap)
-                std::vector<const void*> hs; std::vector<uint32_t*> ds; std::vector<uint8_t> ks;
+                std::vector<const void*> hs; std::vector<uint32_t*> ds; std::vector<uint32_t> call;
                 for (uint32_t k = r.lo; k < r.hi; k++) {
                     if (!h_cols[first + k]) return set_err(p->ctx, NX_ERR_ARG, name + ": NULL host column");
-                    hs.push_back(h_cols[first + k]); ds.push_back(r.slab.p + ((size_t)(k - r.lo) << r.log)); if (kinds) ks.push_back(kinds[first + k]);
+                    hs.push_back(h_cols[first + k]); ds.push_back(r.slab.p + ((size_t)(k - r.lo) << r.log)); call.push_back(first + k);
                 }
-                if (!hs.empty() && !kinds) NX_TRY(nx_upload_columns(p->ctx, (const uint32_t* const*)hs.data(), (uint32_t)hs.size(), r.log, ds.data(), coset_order));
-                if (!hs.empty() && kinds) {
-                    std::vector<uint32_t> call(hs.size());
-                    for (size_t k = 0; k < call.size(); k++) call[k] = first + r.lo + (uint32_t)k;
-                    NX_TRY(upload_columns_narrow(p->ctx, hs.data(), ks.data(), (uint32_t)hs.size(), r.log, ds.data(), coset_order, call.data(), what.c_str()));
-                }
+                if (!hs.empty())
+                    NX_TRY(upload_columns(p->ctx, hs.data(), kinds ? kinds + first + r.lo : nullptr, (uint32_t)hs.size(), r.log, ds.data(), coset_order, call.data(), what.c_str()));
                 for (uint32_t k = 0; k < n_keep; k++)
                     if (keep_idx[k] >= first + r.lo && keep_idx[k] < first + r.hi) NX_TRY(nx_copy(p->ctx, d_keep[k], r.slab.p + ((size_t)(keep_idx[k] - first - r.lo) << r.log), (size_t)1 << r.log));
                 tb.extend_evals_local(std::move(r.slab), r.n_cols, r.log, r.lo, r.hi);
@@ -2036,8 +2031,7 @@ static int tree_commit_host(nx_prover* p, const void* const* h_cols, const uint8
                 for (uint32_t k = 0; k < r.n_cols; k++) if (!h_cols[first + k]) return set_err(p->ctx, NX_ERR_ARG, name + ": NULL host column");
                 std::vector<std::pair<uint32_t, uint32_t*>> keep;
                 for (uint32_t k = 0; k < n_keep; k++) if (keep_idx[k] >= first && keep_idx[k] < first + r.n_cols) keep.push_back({keep_idx[k] - first, d_keep[k]});
-                if (kinds) tb.extend_evals_host(std::move(r.slab), r.n_cols, r.log, h_cols + first, kinds + first, coset_order, keep, first, what.c_str());
-                else tb.extend_evals_host(std::move(r.slab), r.n_cols, r.log, (const uint32_t* const*)h_cols + first, coset_order, keep);
+                tb.extend_evals_host(std::move(r.slab), r.n_cols, r.log, h_cols + first, kinds ? kinds + first : nullptr, coset_order, keep, first, what.c_str());
             }
             first += r.n_cols;
         }

@@ -172,6 +172,15 @@ def test_layout_permutations(be, oracle):
         ref = nat[0].copy()
         oracle.lib().orc_bit_reverse(O.ptr(ref), log)
         assert np.array_equal(br.to_cpu()[0], ref)
+    # whole-trace upload across 16-column chunks of the host feed, one column pinned by its owner (nx_host_pin)
+    many = list(rand_cols(200, 19, 13))
+    many[17] = many[17].copy()
+    be.host_pin(many[17])
+    try:
+        assert np.array_equal(be.upload_columns(many).to_cpu(), np.stack([oracle.finalize_column(c) for c in many]))
+        assert np.array_equal(be.upload_columns(many, coset_order=False).to_cpu(), np.stack(many))
+    finally:
+        be.host_unpin(many[17])
     # the reference's own test_order (prover/src/trace/utils.rs:117-128) at log 3
     vals = np.arange(8, dtype=np.uint32)
     col = be.finalize_columns(be.columns_from_host(vals)).to_cpu()[0]
