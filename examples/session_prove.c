@@ -5,7 +5,10 @@
  * One component of 2^6 rows: main columns a, b, c with the constraint c - a*b - 3 = 0, recorded as the straight-line program a
  * recording EvalAtRow would emit (NX_C_* opcodes); a one-column preprocessed tree and an empty interaction tree complete the
  * three trace trees the protocol expects (reference prover/src/machine.rs:208-263).  Prints "ok <proof words>"; with the argument
- * "bad" it corrupts one trace cell first and expects NX_ERR_PROTOCOL (ProvingError::ConstraintsNotSatisfied). */
+ * "bad" it corrupts one trace cell first and expects NX_ERR_PROTOCOL (ProvingError::ConstraintsNotSatisfied).
+ * The proof is then checked by the verifier session (nx_verifier_*: host only, no context) with the same transcript prefix, the three
+ * roots the prover returned and the same component: "verified: accepted", and, with one word of the proof flipped,
+ * "verified: refused (<the failing check>)". */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -27,10 +30,10 @@ int main(int argc, char** argv) {
     /* tree 0: one preprocessed column (zeros) */
     uint32_t logs[3] = {log, log, log};
     uint32_t* d_pre[1]; uint32_t* d_main[3];
-    uint8_t root[32];
+    uint8_t roots[3][32];
     CHECK(nx_prover_tree_begin(pr, logs, 1, d_pre));
     CHECK(nx_memset_zero(ctx, d_pre[0], n));
-    CHECK(nx_prover_tree_commit(pr, root));
+    CHECK(nx_prover_tree_commit(pr, roots[0]));
 
     /* tree 1: a, b, c = a*b + 3 (the constraint is row-local, so any row order is a valid trace) */
     uint32_t* h = (uint32_t*)malloc(3 * n * sizeof(uint32_t));
@@ -41,12 +44,12 @@ int main(int argc, char** argv) {
     if (bad) h[2 * n + 7] = (h[2 * n + 7] + 1) % P;
     CHECK(nx_prover_tree_begin(pr, logs, 3, d_main));
     for (int k = 0; k < 3; k++) CHECK(nx_upload(ctx, d_main[k], h + k * n, n));
-    CHECK(nx_prover_tree_commit(pr, root));
+    CHECK(nx_prover_tree_commit(pr, roots[1]));
     free(h);
 
     /* tree 2: no interaction columns */
     CHECK(nx_prover_tree_begin(pr, NULL, 0, NULL));
-    CHECK(nx_prover_tree_commit(pr, root));
+    CHECK(nx_prover_tree_commit(pr, roots[2]));
 
     /* the recorded constraint: r3 = a*b; r4 = 3; r3 = r3 + r4; r2 = c - r3; add_constraint(r2) */
     const nx_cinstr prog[] = {
@@ -69,6 +72,22 @@ int main(int argc, char** argv) {
     }
     if (rc != NX_OK) { fprintf(stderr, "nx_prover_prove failed (%d): %s\n", rc, nx_last_error(ctx)); return 1; }
     printf("ok %zu\n", n_words);
+
+    /* the verifier: the same transcript prefix, the roots instead of the columns, the same component; then one word flipped */
+    for (int flip = 0; flip < 2; flip++) {
+        nx_verifier* vf = NULL;
+        if (nx_verifier_create(&cfg, (int)cfg.hash_mode, &vf) != NX_OK) { fprintf(stderr, "nx_verifier_create failed\n"); return 1; }
+        int vrc = nx_verifier_mix_u64(vf, log);
+        if (vrc == NX_OK) vrc = nx_verifier_tree_commit(vf, roots[0], logs, 1);
+        if (vrc == NX_OK) vrc = nx_verifier_tree_commit(vf, roots[1], logs, 3);
+        if (vrc == NX_OK) vrc = nx_verifier_tree_commit(vf, roots[2], NULL, 0);
+        if (vrc != NX_OK) { fprintf(stderr, "verifier transcript failed (%d): %s\n", vrc, nx_verifier_last_error(vf)); return 1; }
+        if (flip) proof[n_words / 2] ^= 1u;
+        vrc = nx_verifier_verify(vf, &comp, 1, proof, n_words);
+        if (vrc == NX_OK) printf("verified: accepted\n"); else printf("verified: refused (%s)\n", nx_verifier_last_error(vf));
+        nx_verifier_destroy(vf);
+        if ((vrc == NX_OK) == (flip != 0) || (flip && vrc != NX_ERR_VERIFY && vrc != NX_ERR_ARG)) { fprintf(stderr, "UNEXPECTED verdict %d\n", vrc); return 1; }
+    }
     nx_free_host(proof);
     nx_prover_destroy(pr);
     nx_ctx_destroy(ctx);

@@ -38,6 +38,7 @@ extern "C" {
 #define NX_ERR_OOM (-3)       /* device or host allocation failed                                   */
 #define NX_ERR_PROTOCOL (-4)  /* ProvingError::ConstraintsNotSatisfied / FRI invalid degree         */
 #define NX_ERR_NO_DEVICE (-5) /* no gfx950 device visible — there is NO CPU fallback                */
+#define NX_ERR_VERIFY (-6)    /* VerificationError: a well-formed proof failed a check of the verifier */
 
 /* Merkle hash rule (unverifiable upstream detail kept switchable). */
 #define NX_HASH_BLAKE2S 0      /* standard Blake2s-256 of (left ‖ right ‖ column values)            */
@@ -91,6 +92,10 @@ int nx_sync(nx_ctx* ctx);
  * another context, process or library on the same GPU can then use that memory.  Synchronises the context. */
 int nx_ctx_trim(nx_ctx* ctx);
 void* nx_ctx_stream(nx_ctx* ctx); /* hipStream_t the context launches on                       */
+/* The context allocator's own count: bytes of device memory it has handed out and not taken back (nx_alloc and every internal buffer;
+ * cached free blocks are not counted), and the high-water mark of that count since the last reset (reset_peak != 0: the mark restarts
+ * at the current count).  Either pointer may be NULL.  Host only.  How nx_commit_root's memory bound is checked. */
+int nx_ctx_memory(nx_ctx* ctx, uint64_t* live_bytes, uint64_t* peak_bytes, int reset_peak);
 const char* nx_version(void);
 
 /* ------------------------------------------- columns: Column / ColumnOps ------------------- */
@@ -642,6 +647,65 @@ typedef struct {
 int nx_prover_prove(nx_prover* prover, const nx_air_component* components, uint32_t n_components, uint32_t** proof_words,
                     size_t* n_words, nx_prove_stats* stats);
 
+/* ------------------------------------------- the verifier session: core::verifier::verify over recorded AIRs
+ * `nexus_vm_prover::verify` (reference prover/src/lib.rs:26-33; prover/src/machine.rs:299-485; prover2/machine/src/verify.rs:28-143)
+ * around Stwo's core::verifier::verify, CommitmentSchemeVerifier, FriVerifier and MerkleVerifier, mirroring the prover session one to
+ * one: the caller replays the transcript prefix — mix the program description (machine.rs:437-446), commit the preprocessed root
+ * (:447-449, verify.rs:60-70), the main root, draw the lookup elements (:451), mix the claimed sums (:448-450 of the prover's order,
+ * machine.rs:262), commit the interaction root — and nx_verifier_verify checks the proof.
+ * HOST ONLY: the verifier is KBs of hashing and a few hundred field operations whatever the trace size; it takes no context and runs in
+ * a process that sees no GPU (nx_ctx_create fails there with NX_ERR_NO_DEVICE).  The node-hash rule a context otherwise holds is the
+ * hash_mode argument (NX_HASH_*; cfg->hash_mode is NOT read).  The one step whose cost grows with the trace — re-committing the
+ * preprocessed columns to compare the root (machine.rs:363-417, verify.rs:103-143) — is nx_commit_root below, on the device.
+ * Returns: NX_OK accepted; NX_ERR_VERIFY a well-formed proof failed a check; NX_ERR_ARG words that cannot be parsed (truncated, a count
+ * beyond the stream, a field word >= p, trailing words) or an inconsistent statement.  nx_verifier_last_error names the failing check
+ * ("tree 1: Merkle root mismatch", "proof of work", "FRI layer 3: Merkle root mismatch" ...).
+ * UNTRUSTED INPUT: proof words come from outside; every count in the stream is bounded by the remaining words and by the statement
+ * before anything is allocated or indexed. */
+typedef struct nx_verifier nx_verifier;
+int nx_verifier_create(const nx_pcs_config* cfg, int hash_mode, nx_verifier** out);
+void nx_verifier_destroy(nx_verifier* verifier);
+const char* nx_verifier_last_error(const nx_verifier* verifier);
+/* Blake2sChannel of the session: as nx_prover_mix_u64 / _mix_felts / _draw_felt / _draw_felts / _channel_digest */
+int nx_verifier_mix_u64(nx_verifier* verifier, uint64_t v);
+int nx_verifier_mix_felts(nx_verifier* verifier, const uint32_t* felts, uint32_t n_felts);
+int nx_verifier_draw_felt(nx_verifier* verifier, uint32_t out[4]);
+int nx_verifier_draw_felts(nx_verifier* verifier, uint32_t n_felts, uint32_t* out);
+int nx_verifier_channel_digest(const nx_verifier* verifier, uint8_t digest[32]);
+/* CommitmentSchemeVerifier::commit (machine.rs:447-482): the root of the next tree and its columns' log sizes (the trace sizes, as
+ * nx_prover_tree_begin takes them); mixes the root. */
+int nx_verifier_tree_commit(nx_verifier* verifier, const uint8_t root[32], const uint32_t* log_sizes, uint32_t n_cols);
+/* The same with the root COMPUTED from the columns on the device (nx_commit_root): the verifier's re-commit of the preprocessed trace
+ * (machine.rs:363-417; verify.rs:103-143).  d_cols as nx_commit_root takes them (consumed: they hold coefficients afterwards).  The
+ * context's hash mode must be the session's. */
+int nx_verifier_tree_commit_columns(nx_verifier* verifier, nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, const uint32_t* log_sizes,
+                                    uint32_t n_cols, uint8_t root[32]);
+/* core::verifier::verify (machine.rs:483-485, verify.rs:134-143) of an NXP1 proof against the committed roots: the same component array
+ * nx_prover_prove takes (`kernel` is ignored); every recorded program runs once, at the out-of-domain point, over QM31 on the host.
+ * Checks, in order: the proof's shape against the committed column sizes and masks; the commitments against the committed roots; the
+ * composition value at the out-of-domain point; the FRI commit phase replayed on the channel (both fri_alpha_mode values); proof of
+ * work; query positions; every Merkle decommitment (both node-hash rules, mixed-degree trees); the DEEP quotients at the queried
+ * positions; every FRI layer and the last-layer polynomial.  After NX_OK nx_verifier_channel_digest is the transcript's final state;
+ * another call starts again from the state the first one found and a refusal restores it at once, so verifying again gives the same
+ * answer. */
+int nx_verifier_verify(nx_verifier* verifier, const nx_air_component* components, uint32_t n_components, const uint32_t* proof_words,
+                       size_t n_words);
+/* `nexus_vm_prover::verify` for the machine of nx_prove_machine (machine.rs:363-500): replays the transcript prefix as nx_prove_machine
+ * writes it (ad bytes, log sizes, the preprocessed and main roots out of the proof, lookup elements drawn, claimed sums mixed, the
+ * interaction root), rebuilds the components from the drawn elements and the claimed sums (4 words per component: `Proof.claimed_sum`,
+ * nx_machine_claimed_sums) with nx_machine_air_program's emitter, and verifies.  expected_logup_sum (4 words, or NULL): the value the
+ * claimed sums must add up to — verify_logup_sum (prover2/machine/src/verify.rs:145-160) compares their sum with the memory boundary's
+ * expected sum, a function of public data; the synthetic machine has no such public value, so its caller passes the sum it expects or
+ * NULL for no check.  A caller that also holds the preprocessed columns compares proof root 0 with nx_commit_root of them.
+ * err_text (optional, err_cap bytes): the failing check.  Host only. */
+int nx_verify_machine(const nx_component_spec* comps, uint32_t n_comps, const nx_pcs_config* cfg, int hash_mode, const uint8_t* ad,
+                      size_t ad_len, const uint32_t* proof_words, size_t n_words, const uint32_t* claimed_sums,
+                      const uint32_t* expected_logup_sum, char* err_text, size_t err_cap);
+/* The counterpart of nx_prove_synth: its transcript prefix and the synthetic AIR's constraints evaluated at the out-of-domain point on
+ * the host (the proving side has them as a device kernel only).  Host only. */
+int nx_verify_synth(const nx_component_spec* comps, uint32_t n_comps, const nx_pcs_config* cfg, int hash_mode, const uint8_t* ad,
+                    size_t ad_len, const uint32_t* proof_words, size_t n_words, char* err_text, size_t err_cap);
+
 /* ------------------------------------------- "next" row R8: logup interaction trace on device ------------------------
  * The reference fills the interaction trace on the CPU (prover/src/traits.rs:124-145 generate_interaction_trace -> per chip,
  * e.g. prover/src/chips/range_check/range256.rs:271-288; prover2/machine/src/lookups/logup_trace_builder.rs:22-121) through
@@ -707,6 +771,25 @@ int nx_logup_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_instr, ui
  * bit-reversed evaluations, overwritten by their coefficients); d_lde receives the LDE columns. */
 int nx_lde_commit(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, uint32_t n_cols, uint32_t log_size,
                   uint32_t log_blowup, uint32_t* const* d_lde, uint8_t root[32]);
+
+/* The ROOT of that commitment without keeping the extension or the tree — what a verifier needs of the preprocessed columns: the
+ * reference re-commits them at full height in every verification only to compare 32 bytes (prover/src/machine.rs:363-417,
+ * prover2/machine/src/verify.rs:103-143).  d_cols: n_cols columns in commit order, column i of 2^log_sizes[i] words
+ * (trace sizes, mixed sizes allowed; bit-reversed evaluations on entry, CONSUMED like nx_lde_commit's: they hold the coefficients on
+ * return).  The columns of the largest size are extended in chunks of C = 16 (one Blake2s block of the leaf chain) into a ring of R = 2
+ * slots and absorbed by the leaf chain while the next chunk transforms; no extension outlives its chunk.  The inner layers are reduced
+ * to the root three levels per launch between two buffers, none of them stored.  Same root as nx_lde_commit / nx_prover_tree_commit of
+ * the same columns, for both node-hash rules; n_cols = 0 gives the root of the empty tree.
+ * DEVICE MEMORY: with M = 2^(max log_size + log_blowup) rows, n the number of columns of the largest size and S the smaller columns,
+ *     peak above the inputs  <=  4 M min(C, n) min(R, ceil(n / C))      the ring
+ *                              + 32 M                                    the running leaf state
+ *                              + 32 M / 2^k                              the second reduction buffer; k = 3 when all columns have one size,
+ *                                                                        else min(3, max(1, d - 1)) with 2^d = largest size / next smaller size
+ *                              + sum over S of 4 * 2^(log_size + log_blowup)   smaller columns, kept whole until their layer is hashed
+ * bytes, each term rounded up to 256 — independent of n beyond the ring.  (nx_lde_commit: 4 M n for the extensions plus 64 M for the tree.)
+ * Blocking (returns the root). */
+int nx_commit_root(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, const uint32_t* log_sizes, uint32_t n_cols,
+                   uint32_t log_blowup, uint8_t root[32]);
 
 #ifdef __cplusplus
 }

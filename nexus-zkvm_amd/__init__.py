@@ -272,6 +272,27 @@ class AirComponentC(C.Structure):
                 ("mask_count", C.c_void_p), ("mask_offsets", C.c_void_p), ("kernel", C.c_void_p), ("log_constraint_degree_bound", C.c_uint32)]
 
 
+def _air_components(components, kernels=None):
+    """air_program.Component list -> the nx_air_component array of nx_prover_prove / nx_verifier_verify (and the arrays it points into)."""
+    arr = (AirComponentC * len(components))()
+    keep = []
+    for i, c in enumerate(components):
+        pr = c.program
+        ins, ec = _u32(pr.instrs).reshape(-1), _u32(pr.econsts).reshape(-1)
+        ct, ci = _u32([t for t, _ in c.cols]), _u32([k for _, k in c.cols])
+        mc = _u32([len(m) for m in c.masks])
+        mo = np.ascontiguousarray([o for m in c.masks for o in m], dtype=np.int32)
+        keep += [ins, ec, ct, ci, mc, mo]
+        a = arr[i]
+        a.log_size, a.program, a.n_instr, a.n_regs = c.log_size, ins.ctypes.data, len(ins) // 4, pr.n_regs
+        a.econsts, a.n_econsts, a.n_constraints = ec.ctypes.data if len(ec) else None, len(ec) // 4, pr.n_constraints
+        a.col_tree, a.col_index, a.n_cols = ct.ctypes.data if len(ct) else None, ci.ctypes.data if len(ci) else None, len(c.cols)
+        a.mask_count, a.mask_offsets = mc.ctypes.data if len(mc) else None, mo.ctypes.data if len(mo) else None
+        a.kernel = kernels[i].h if kernels else None
+        a.log_constraint_degree_bound = getattr(c, "log_constraint_degree_bound", 0)
+    return arr, keep
+
+
 class ProverSession:
     """nx_prover_*: CommitmentSchemeProver + Blake2sChannel + stwo::prover::prove over recorded AIRs
     (air_program.Component).  The caller drives the reference's transcript prefix (machine.rs:198-263)."""
@@ -371,22 +392,7 @@ class ProverSession:
 
     def prove(self, components, kernels=None, want_stats=False):
         """components: air_program.Component list; kernels: optional AirKernel per component (compiled once, reused)."""
-        arr = (AirComponentC * len(components))()
-        keep = []
-        for i, c in enumerate(components):
-            pr = c.program
-            ins, ec = _u32(pr.instrs).reshape(-1), _u32(pr.econsts).reshape(-1)
-            ct, ci = _u32([t for t, _ in c.cols]), _u32([k for _, k in c.cols])
-            mc = _u32([len(m) for m in c.masks])
-            mo = np.ascontiguousarray([o for m in c.masks for o in m], dtype=np.int32)
-            keep += [ins, ec, ct, ci, mc, mo]
-            a = arr[i]
-            a.log_size, a.program, a.n_instr, a.n_regs = c.log_size, ins.ctypes.data, len(ins) // 4, pr.n_regs
-            a.econsts, a.n_econsts, a.n_constraints = ec.ctypes.data if len(ec) else None, len(ec) // 4, pr.n_constraints
-            a.col_tree, a.col_index, a.n_cols = ct.ctypes.data if len(ct) else None, ci.ctypes.data if len(ci) else None, len(c.cols)
-            a.mask_count, a.mask_offsets = mc.ctypes.data if len(mc) else None, mo.ctypes.data if len(mo) else None
-            a.kernel = kernels[i].h if kernels else None
-            a.log_constraint_degree_bound = getattr(c, "log_constraint_degree_bound", 0)
+        arr, keep = _air_components(components, kernels)
         words, n = C.POINTER(C.c_uint32)(), C.c_size_t(0)
         stats = ProveStats()
         self.be._chk(self.be.L.nx_prover_prove(self.h, arr, len(components), C.byref(words), C.byref(n), C.byref(stats) if want_stats else None))
@@ -427,6 +433,121 @@ class SharedTree:
             self.release()
         except Exception:
             pass
+
+
+NX_ERR_ARG, NX_ERR_VERIFY = -2, -6
+
+
+class VerifierSession:
+    """nx_verifier_*: CommitmentSchemeVerifier + Blake2sChannel + core::verifier::verify over recorded AIRs, the mirror of ProverSession
+    (reference prover/src/machine.rs:299-485).  Host only: needs no HipBackend and no GPU.  hash_mode: the node-hash rule (default: the
+    config's)."""
+
+    def __init__(self, cfg, hash_mode=None):
+        self.L, self.cfg = load_library(), cfg
+        self.h = C.c_void_p()
+        rc = self.L.nx_verifier_create(C.byref(cfg), int(cfg.hash_mode if hash_mode is None else hash_mode), C.byref(self.h))
+        if rc != NX_OK:
+            raise NexusHipError(f"nx_verifier_create failed (rc={rc}): configuration outside the verifier's range")
+
+    def _chk(self, rc):
+        if rc != NX_OK:
+            raise NexusHipError(f"libnexus_hip verifier error {rc}: {self.last_error()}")
+
+    def last_error(self):
+        return self.L.nx_verifier_last_error(self.h).decode()
+
+    def mix_u64(self, v):
+        self._chk(self.L.nx_verifier_mix_u64(self.h, C.c_uint64(int(v))))
+
+    def mix_felts(self, felts):
+        f = _u32(felts).reshape(-1)
+        self._chk(self.L.nx_verifier_mix_felts(self.h, f.ctypes.data_as(C.c_void_p), len(f) // 4))
+
+    def draw_felt(self):
+        out = np.zeros(4, np.uint32)
+        self._chk(self.L.nx_verifier_draw_felt(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def draw_felts(self, n):
+        out = np.zeros((n, 4), np.uint32)
+        self._chk(self.L.nx_verifier_draw_felts(self.h, n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def digest(self):
+        out = np.zeros(8, np.uint32)
+        self._chk(self.L.nx_verifier_channel_digest(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def commit(self, root, log_sizes):
+        """CommitmentSchemeVerifier::commit: the root (8 words) of the next tree and its columns' trace log sizes."""
+        r, logs = _u32(root), _u32(log_sizes)
+        self._chk(self.L.nx_verifier_tree_commit(self.h, r.ctypes.data_as(C.c_void_p), logs.ctypes.data_as(C.c_void_p), len(logs)))
+
+    def commit_columns(self, be, tw, column_sets):
+        """The same with the root computed from device columns (HipBackend.commit_root; the columns are consumed).  Returns the root."""
+        ptrs, logs = [], []
+        for s in column_sets:
+            ptrs += [s.ptr.value + i * (4 << s.log_size) for i in range(s.n_cols)]
+            logs += [s.log_size] * s.n_cols
+        arr, lg, root = (C.c_void_p * max(1, len(ptrs)))(*ptrs), _u32(logs), np.zeros(8, np.uint32)
+        rc = self.L.nx_verifier_tree_commit_columns(self.h, be.ctx, tw.h, arr, lg.ctypes.data_as(C.c_void_p), len(logs), root.ctypes.data_as(C.c_void_p))
+        if rc != NX_OK:
+            raise NexusHipError(f"nx_verifier_tree_commit_columns failed (rc={rc}): {self.last_error() or be.L.nx_last_error(be.ctx).decode()}")
+        return root
+
+    def verify(self, components, words):
+        """None when the proof is accepted, else the text of the failing check (self.rc: NX_ERR_VERIFY or NX_ERR_ARG)."""
+        arr, keep = _air_components(components)
+        w = _u32(words)
+        self.rc = self.L.nx_verifier_verify(self.h, arr, len(components), w.ctypes.data_as(C.c_void_p), C.c_size_t(len(w)))
+        del keep
+        return None if self.rc == NX_OK else self.last_error()
+
+    def close(self):
+        if self.h:
+            self.L.nx_verifier_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _comp_specs(comps):
+    return (ComponentSpec * len(comps))(*[ComponentSpec(*[int(x) for x in c]) for c in comps])
+
+
+def verify_synth(comps, cfg, words, ad=b"", hash_mode=None, want_rc=False):
+    """nx_verify_synth — `nexus_vm_prover::verify` for the synthetic machine of HipBackend.prove.  Host only.  None when accepted, else
+    the failing check; want_rc: (text or None, return code)."""
+    L = load_library()
+    w, err = _u32(words), C.create_string_buffer(512)
+    adb = (C.c_uint8 * max(1, len(ad)))(*ad)
+    rc = L.nx_verify_synth(_comp_specs(comps), len(comps), C.byref(cfg), int(cfg.hash_mode if hash_mode is None else hash_mode), adb, C.c_size_t(len(ad)),
+                           w.ctypes.data_as(C.c_void_p), C.c_size_t(len(w)), err, C.c_size_t(len(err)))
+    text = None if rc == NX_OK else (err.value.decode() or f"error {rc}")
+    return (text, rc) if want_rc else text
+
+
+def verify_machine(comps, cfg, words, claimed_sums, ad=b"", hash_mode=None, expected_logup_sum=None, want_rc=False):
+    """nx_verify_machine — `nexus_vm_prover::verify` for the machine of HipBackend.prove_machine; claimed_sums: (n_components, 4) words
+    (HipBackend.machine_claimed_sums); expected_logup_sum: 4 words the claimed sums must add up to, or None for no such check.
+    Host only.  None when accepted, else the failing check."""
+    L = load_library()
+    w, err = _u32(words), C.create_string_buffer(512)
+    cs = _u32(claimed_sums).reshape(-1)
+    if len(cs) != 4 * len(comps):
+        raise ValueError("claimed_sums: 4 words per component")
+    ex = _u32(expected_logup_sum).reshape(4) if expected_logup_sum is not None else None
+    adb = (C.c_uint8 * max(1, len(ad)))(*ad)
+    rc = L.nx_verify_machine(_comp_specs(comps), len(comps), C.byref(cfg), int(cfg.hash_mode if hash_mode is None else hash_mode), adb, C.c_size_t(len(ad)),
+                             w.ctypes.data_as(C.c_void_p), C.c_size_t(len(w)), cs.ctypes.data_as(C.c_void_p),
+                             ex.ctypes.data_as(C.c_void_p) if ex is not None else None, err, C.c_size_t(len(err)))
+    text = None if rc == NX_OK else (err.value.decode() or f"error {rc}")
+    return (text, rc) if want_rc else text
 
 
 class LogupFrac(C.Structure):
@@ -470,6 +591,10 @@ def load_library():
     L.nx_comm_local_destroy.argtypes = [C.c_void_p]
     L.nx_committed_tree_release.argtypes = [C.c_void_p]
     L.nx_committed_tree_release.restype = None
+    L.nx_verifier_destroy.argtypes = [C.c_void_p]
+    L.nx_verifier_destroy.restype = None
+    L.nx_verifier_last_error.argtypes = [C.c_void_p]
+    L.nx_verifier_last_error.restype = C.c_char_p
     for name in ("nx_ctx_destroy", "nx_twiddles_destroy", "nx_tree_destroy", "nx_free_host", "nx_air_kernel_destroy", "nx_prover_destroy", "nx_comm_group_destroy",
                  "nx_comm_local_destroy", "nx_comm_rccl_destroy"):
         getattr(L, name).restype = None
@@ -785,6 +910,23 @@ class HipBackend:
         self._chk(self.L.nx_lde_commit(self.ctx, tw.h, cols.col_ptrs(), cols.n_cols, cols.log_size, log_blowup, out.col_ptrs(),
                                        root.ctypes.data_as(C.c_void_p)))
         return out, root
+
+    def commit_root(self, tw, column_sets, log_blowup):
+        """nx_commit_root: the Merkle root of the LDE of the columns (DeviceColumns sets in commit order, mixed sizes allowed) without
+        keeping the extension or the tree.  The columns are consumed (they hold coefficients afterwards)."""
+        ptrs, logs = [], []
+        for s in column_sets:
+            ptrs += [s.ptr.value + i * (4 << s.log_size) for i in range(s.n_cols)]
+            logs += [s.log_size] * s.n_cols
+        arr, lg, root = (C.c_void_p * max(1, len(ptrs)))(*ptrs), _u32(logs), np.empty(8, np.uint32)
+        self._chk(self.L.nx_commit_root(self.ctx, tw.h if tw is not None else None, arr, lg.ctypes.data_as(C.c_void_p), len(logs), log_blowup, root.ctypes.data_as(C.c_void_p)))
+        return root
+
+    def memory(self, reset_peak=False):
+        """nx_ctx_memory: (live bytes, peak live bytes since the last reset) of the context's device allocator."""
+        live, peak = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.nx_ctx_memory(self.ctx, C.byref(live), C.byref(peak), int(bool(reset_peak))))
+        return live.value, peak.value
 
     def eval_at_points(self, polys, poly_idx, points):
         idx = _u32(poly_idx)

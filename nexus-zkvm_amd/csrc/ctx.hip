@@ -145,6 +145,7 @@ int dev_alloc(nx_ctx* ctx, size_t bytes, void** out) {
     if (it != ctx->free_blocks.end()) {
         *out = it->second; ctx->free_blocks.erase(it); ctx->cached_bytes -= bytes;
         ctx->live_blocks[*out] = bytes;
+        ctx->live_bytes += bytes; ctx->peak_live_bytes = std::max(ctx->peak_live_bytes, ctx->live_bytes);
         return NX_OK;
     }
     hipError_t e = hipMalloc(out, bytes);
@@ -155,6 +156,7 @@ int dev_alloc(nx_ctx* ctx, size_t bytes, void** out) {
     }
     if (e != hipSuccess) { *out = nullptr; return hip_fail(ctx, e, "hipMalloc", __FILE__, __LINE__); }
     ctx->live_blocks[*out] = bytes;
+    ctx->live_bytes += bytes; ctx->peak_live_bytes = std::max(ctx->peak_live_bytes, ctx->live_bytes);
     return NX_OK;
 }
 void dev_free(nx_ctx* ctx, void* p) {
@@ -163,6 +165,7 @@ void dev_free(nx_ctx* ctx, void* p) {
     if (it == ctx->live_blocks.end()) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(p); return; }  // foreign pointer
     ctx->free_blocks.insert({it->second, p});
     ctx->cached_bytes += it->second;
+    ctx->live_bytes -= it->second;
     ctx->live_blocks.erase(it);
     if (ctx->cached_bytes > ((size_t)192 << 30)) dev_cache_release(ctx);  // keep the cache bounded (a 2^24-row prove recycles ~100 GB)
 }
@@ -448,6 +451,13 @@ int nx_ctx_set_hash_mode(nx_ctx* ctx, int mode) {
 int nx_sync(nx_ctx* ctx) { NX_GUARD(ctx); if (!ctx) return set_err(nullptr, NX_ERR_ARG, "nx_sync: NULL context"); NX_HIP(ctx, hipStreamSynchronize(ctx->stream)); return NX_OK; }
 int nx_ctx_trim(nx_ctx* ctx) { NX_GUARD(ctx); if (!ctx) return set_err(nullptr, NX_ERR_ARG, "nx_ctx_trim: NULL context"); NX_TRY(nx_sync(ctx)); dev_cache_release(ctx); pack_ring_release(ctx); return NX_OK; }
 void* nx_ctx_stream(nx_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
+int nx_ctx_memory(nx_ctx* ctx, uint64_t* live_bytes, uint64_t* peak_bytes, int reset_peak) {
+    if (!ctx) return set_err(nullptr, NX_ERR_ARG, "nx_ctx_memory: NULL context");
+    if (live_bytes) *live_bytes = ctx->live_bytes;
+    if (peak_bytes) *peak_bytes = ctx->peak_live_bytes;
+    if (reset_peak) ctx->peak_live_bytes = ctx->live_bytes;
+    return NX_OK;
+}
 
 int nx_alloc(nx_ctx* ctx, size_t n_words, uint32_t** d_out) {
     NX_GUARD(ctx);

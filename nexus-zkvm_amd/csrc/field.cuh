@@ -4,10 +4,14 @@
 // All values are canonical ([0, p)) on every load and store: committed columns are hashed as raw
 // u32 words, so `p` (== 0) must never be emitted (SURVEY.md §7 "Canonical representatives").
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
-
+// A plain C++ compiler (the host verifier's CPU build, tests/native/verifier_selftest.cpp) sees the same functions as ordinary inlines.
+#if defined(__HIPCC__) || defined(__HIP__)
+#include <hip/hip_runtime.h>
 #define NX_HD __host__ __device__ __forceinline__
+#else
+#define NX_HD inline
+#endif
 
 namespace nx {
 

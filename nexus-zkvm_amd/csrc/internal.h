@@ -71,6 +71,7 @@ struct nx_ctx {
     std::multimap<size_t, void*> free_blocks;
     std::map<void*, size_t> live_blocks;
     size_t cached_bytes;
+    size_t live_bytes = 0, peak_live_bytes = 0;      // sum of live_blocks and its high-water mark since the last reset (nx_ctx_memory)
     // pinned host blocks cached by exact size: targets of asynchronous device-to-host copies that must outlive later stage() calls
     // (the partial sums of every OODS request of a proof are collected after ONE synchronisation)
     std::multimap<size_t, void*> free_pinned;
@@ -300,6 +301,7 @@ int tree_pipe_begin(nx_ctx* ctx, uint32_t max_log, uint32_t total_leaf_cols, Tre
 int tree_pipe_absorb(nx_ctx* ctx, TreePipe* tp, const uint32_t* const* d_cols, uint32_t n_cols, bool flush);
 // smaller columns (log < max_log) in commit order with their sizes; hands the finished tree to *out
 int tree_pipe_finish(nx_ctx* ctx, TreePipe* tp, const uint32_t* const* d_small_cols, const uint32_t* small_logs, uint32_t n_small, nx_tree** out);
+int leaf_chain_launch(nx_ctx* ctx, ColSet cs, uint32_t n_cols, uint32_t col_offset, uint32_t total_cols, const uint32_t* state_in, uint32_t* state_out, uint64_t row_begin, uint64_t n_rows);
 int fft_lde(nx_ctx* ctx, const nx_twiddles* tw, ColSet cols, uint32_t n_cols, uint32_t log_size, uint32_t log_expand, ColSet out);
 
 // fork/join of the side streams around a loop over independent column batches

@@ -931,4 +931,76 @@ int nx_machine_claimed_sums(const nx_ctx* ctx, uint32_t* claimed_sums, uint32_t 
     return NX_OK;
 }
 
+// `nexus_vm_prover::verify` for this machine (reference prover/src/machine.rs:363-500, prover2/machine/src/verify.rs:28-160) on the host
+// verifier session (host/verifier.cpp): the transcript prefix exactly as prove_machine above writes it, the components from the same
+// emitter (machine_component, fill_econsts) with the lookup elements the verifier drew itself and the claimed sums of the statement.
+int nx_verify_machine(const nx_component_spec* comps, uint32_t n_comps, const nx_pcs_config* cfg, int hash_mode, const uint8_t* ad, size_t ad_len,
+                      const uint32_t* proof_words, size_t n_words, const uint32_t* claimed_sums, const uint32_t* expected_logup_sum, char* err_text, size_t err_cap) {
+    auto fail = [&](int rc, const std::string& s) { if (err_text && err_cap) snprintf(err_text, err_cap, "%s", s.c_str()); return rc; };
+    if (err_text && err_cap) err_text[0] = 0;
+    if (!comps || !n_comps || !cfg || (ad_len && !ad) || (n_words && !proof_words) || !claimed_sums) return fail(NX_ERR_ARG, "nx_verify_machine: NULL argument or no components");
+    if (cfg->log_constraint_degree < 1 || cfg->log_constraint_degree > 2) return fail(NX_ERR_ARG, "nx_verify_machine: log_constraint_degree in {1,2} required");
+    for (uint32_t i = 0; i < n_comps; i++) {
+        const nx_component_spec& c = comps[i];
+        if (c.n_pre < 2 || c.n_main < 2 || c.log_size < 1 || c.log_size > 28 || c.n_inter % 4 || !nxhip::logup_mode_ok(c.logup_mode) ||
+            !nxhip::comp_log_cd_ok(c.log_constraint_degree_bound, cfg->log_constraint_degree) || c.n_pre > (1u << 20) || c.n_main > (1u << 20) || c.n_inter > (1u << 20))
+            return fail(NX_ERR_ARG, "nx_verify_machine: a component nx_prove_machine would refuse");
+        for (int q = 0; q < 4; q++) if (claimed_sums[4 * (size_t)i + q] >= P) return fail(NX_ERR_ARG, "nx_verify_machine: claimed sum not canonical");
+    }
+    // header (5 words), the commitment count, four roots: the three trace roots enter the transcript from the proof itself
+    if (n_words < 6 + 32 || proof_words[0] != 0x3150584Eu) return fail(NX_ERR_ARG, "proof words: not an NXP1 stream of a four-tree proof");
+    if (proof_words[5] != 4) return fail(NX_ERR_VERIFY, "proof shape: the machine commits four trees");
+    if (expected_logup_sum) {            // verify_logup_sum: the claimed sums add up to the value the public data fixes
+        QM31 sum = q_zero();
+        for (uint32_t i = 0; i < n_comps; i++) sum = q_add(sum, q_load(claimed_sums + 4 * (size_t)i));
+        uint32_t w[4]; q_store(w, sum);
+        if (memcmp(w, expected_logup_sum, 16)) return fail(NX_ERR_VERIFY, "claimed logup sum does not add up to the expected sum");
+    }
+    nx_verifier* v = nullptr;
+    int rc = nx_verifier_create(cfg, hash_mode, &v);
+    if (rc != NX_OK) return fail(rc, "nx_verify_machine: configuration outside the verifier's range");
+    struct Guard { nx_verifier* v; ~Guard() { nx_verifier_destroy(v); } } guard{v};
+    auto step = [&](int r) { if (r != NX_OK && rc == NX_OK) rc = r; };
+    for (size_t i = 0; i < ad_len; i++) step(nx_verifier_mix_u64(v, ad[i]));                    // machine.rs:198-200
+    for (uint32_t i = 0; i < n_comps; i++) step(nx_verifier_mix_u64(v, comps[i].log_size));     // machine.rs:204-206
+    uint32_t max_log = 0;
+    const std::vector<nxhip::Loc> locs = nxhip::locations(comps, n_comps, &max_log);
+    std::vector<uint32_t> logs[3];
+    for (uint32_t i = 0; i < n_comps; i++) {
+        logs[0].insert(logs[0].end(), comps[i].n_pre, comps[i].log_size);
+        logs[1].insert(logs[1].end(), comps[i].n_main, comps[i].log_size);
+        logs[2].insert(logs[2].end(), comps[i].n_inter, comps[i].log_size);
+    }
+    const uint8_t* roots = (const uint8_t*)(proof_words + 6);
+    step(nx_verifier_tree_commit(v, roots, logs[0].data(), (uint32_t)logs[0].size()));
+    step(nx_verifier_tree_commit(v, roots + 32, logs[1].data(), (uint32_t)logs[1].size()));
+    uint32_t za[8];
+    step(nx_verifier_draw_felts(v, 2, za));                                                      // machine.rs:239-240
+    step(nx_verifier_mix_felts(v, claimed_sums, n_comps));                                       // machine.rs:262
+    step(nx_verifier_tree_commit(v, roots + 64, logs[2].data(), (uint32_t)logs[2].size()));
+    if (rc != NX_OK) return fail(rc, nx_verifier_last_error(v));
+    const nxhip::PcsConfig pc = {cfg->pow_bits, cfg->log_blowup, cfg->n_queries, cfg->log_last_layer_degree_bound, cfg->fri_alpha_mode, cfg->log_constraint_degree};
+    std::vector<nxhip::GComponent> g(n_comps);
+    std::vector<std::vector<uint32_t>> ct(n_comps), ci(n_comps), mc(n_comps);
+    std::vector<std::vector<int32_t>> mo(n_comps);
+    std::vector<nx_air_component> air(n_comps);
+    for (uint32_t i = 0; i < n_comps; i++) {
+        g[i] = nxhip::machine_component(comps[i], locs[i], pc);
+        const QM31 shift = q_mul_m(q_load(claimed_sums + 4 * (size_t)i), m_inv((1u << comps[i].log_size) % P));
+        nxhip::fill_econsts(g[i].econsts, za, za + 4, shift);
+        for (size_t k = 0; k < g[i].cols.size(); k++) {
+            ct[i].push_back(g[i].cols[k].first); ci[i].push_back(g[i].cols[k].second); mc[i].push_back((uint32_t)g[i].masks[k].size());
+            for (int o : g[i].masks[k]) mo[i].push_back(o);
+        }
+        nx_air_component& a = air[i];
+        memset(&a, 0, sizeof a);
+        a.log_size = comps[i].log_size; a.program = g[i].prog.data(); a.n_instr = (uint32_t)g[i].prog.size(); a.n_regs = g[i].n_regs;
+        a.econsts = g[i].econsts.data(); a.n_econsts = (uint32_t)(g[i].econsts.size() / 4); a.n_constraints = g[i].n_constraints;
+        a.col_tree = ct[i].data(); a.col_index = ci[i].data(); a.n_cols = (uint32_t)g[i].cols.size(); a.mask_count = mc[i].data(); a.mask_offsets = mo[i].data();
+        a.log_constraint_degree_bound = comps[i].log_constraint_degree_bound;
+    }
+    rc = nx_verifier_verify(v, air.data(), n_comps, proof_words, n_words);
+    return rc == NX_OK ? NX_OK : fail(rc, nx_verifier_last_error(v));
+}
+
 }  // extern "C"

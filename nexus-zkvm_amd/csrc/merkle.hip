@@ -14,6 +14,7 @@
 // (merkle_top_kernel); the last FRI layers are committed, mixed into the channel and folded in one launch (fri_tail_kernel),
 // the larger ones get their channel step from fri_channel_kernel — the FRI commit phase never waits for the host.
 #include "internal.h"
+#include "host/verifier.h"
 #include <atomic>
 #include <algorithm>
 #include <numeric>
@@ -171,6 +172,40 @@ __global__ __launch_bounds__(256) void merkle_pair_levels_kernel(const u32* __re
     uint4* o = reinterpret_cast<uint4*>(out + (size_t)i * 8);
     o[0] = make_uint4(h[0], h[1], h[2], h[3]);
     o[1] = make_uint4(h[4], h[5], h[6], h[7]);
+}
+
+// Root-only commits (nx_commit_root): LEVELS node-only levels per launch with NOTHING kept in between.  Thread i owns the subtree over the
+// 2^LEVELS consecutive nodes in[i 2^LEVELS ..] (32 B each, one contiguous 2^LEVELS x 32-B span read as 16-B words, the access pattern of
+// merkle_pair_levels_kernel), hashes it down in registers and writes only its root to out[i]: the levels between are never stored, so a
+// caller ping-pongs two buffers — the dead layer below becomes the output of the launch after next — instead of holding a tree.
+// `in` and `out` must not overlap (another thread's input may be this thread's output slot).
+template <int MODE, int LEVELS>
+__global__ __launch_bounds__(256) void merkle_reduce_kernel(const u32* __restrict__ in, u32* __restrict__ out, u32 n_out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_out) return;
+    constexpr int W = 1 << LEVELS;
+    const u32* p = in + (size_t)i * (8 * W);
+    u32 node[8 * W];
+#pragma unroll
+    for (int k = 0; k < 2 * W; k++) { const uint4 w = gld4(p + 4 * k); node[4 * k] = w.x; node[4 * k + 1] = w.y; node[4 * k + 2] = w.z; node[4 * k + 3] = w.w; }
+#pragma unroll
+    for (int width = W; width > 1; width >>= 1) {
+#pragma unroll
+        for (int j = 0; j < width / 2; j++) {
+            u32 h[8], m[16];
+#pragma unroll
+            for (int k = 0; k < 8; k++) h[k] = MODE == 0 ? B2S_IV_D[k] : 0u;
+            if (MODE == 0) h[0] ^= 0x01010020u;
+#pragma unroll
+            for (int k = 0; k < 16; k++) m[k] = node[16 * j + k];
+            if (MODE == 0) b2s_compress(h, m, 64, 0xFFFFFFFFu); else b2s_compress(h, m, 0, 0);
+#pragma unroll
+            for (int k = 0; k < 8; k++) node[8 * j + k] = h[k];      // slot j of the level above: behind every pair still to be read (8 j + 8 <= 16 j' for j' > j)
+        }
+    }
+    uint4* o = reinterpret_cast<uint4*>(out + (size_t)i * 8);
+    o[0] = make_uint4(node[0], node[1], node[2], node[3]);
+    o[1] = make_uint4(node[4], node[5], node[6], node[7]);
 }
 
 // One column shard of a leaf layer: continue (or start) the per-row chaining state over this shard's columns.
@@ -840,6 +875,61 @@ int tree_pipe_finish(nx_ctx* ctx, TreePipe* tp, const uint32_t* const* d_small_c
     return NX_OK;
 }
 
+// `levels` (1 .. 3) node-only levels from the 2^log_in nodes of `in` to the 2^(log_in - levels) nodes of `out`, nothing kept in between
+static int merkle_reduce(nx_ctx* ctx, const u32* in, u32* out, u32 log_in, int levels) {
+    if (levels < 1 || levels > 3 || (u32)levels > log_in || log_in > 30) return set_err(ctx, NX_ERR_ARG, "merkle_reduce: bad level range");
+    const u32 n_out = 1u << (log_in - levels);
+    const dim3 grid((n_out + 255) / 256), block(256);
+    const bool std_hash = ctx->hash_mode == NX_HASH_BLAKE2S;
+#define NX_REDUCE(L) do { if (std_hash) hipLaunchKernelGGL((merkle_reduce_kernel<0, L>), grid, block, 0, ctx->stream, in, out, n_out); \
+                          else hipLaunchKernelGGL((merkle_reduce_kernel<1, L>), grid, block, 0, ctx->stream, in, out, n_out); } while (0)
+    if (levels == 3) NX_REDUCE(3); else if (levels == 2) NX_REDUCE(2); else NX_REDUCE(1);
+#undef NX_REDUCE
+    NX_LAUNCH_CHECK(ctx);
+    return NX_OK;
+}
+
+// levels the first launch of reduce_to_root takes: it sizes the second buffer (2^(max_log - levels) nodes, the largest output written there)
+static uint32_t first_step_levels(uint32_t max_log, const std::vector<uint32_t>& logs) {
+    if (!logs.empty() && logs[0] + 1 == max_log) return 1;            // a merkle_layer launch: the layer above the leaves injects columns
+    const uint32_t stop = logs.empty() ? 0 : logs[0] + 1;             // lowest layer the first node-only run may produce
+    return std::min<uint32_t>(3, max_log - stop);
+}
+size_t root_scratch_nodes(uint32_t max_log, const std::vector<uint32_t>& logs) {
+    if (max_log == 0) return 1;
+    return (size_t)1 << (max_log - first_step_levels(max_log, logs));
+}
+// The root above a hashed layer of 2^max_log nodes in `a` WITHOUT storing the layers: `a` (2^max_log nodes, consumed) and `b`
+// (root_scratch_nodes(...) nodes) are written in turn, each launch reading the buffer the previous one wrote.  `sorted` / `logs`: the
+// smaller columns, size-descending (a layer that injects columns is one merkle_layer launch, the runs of node-only levels go three
+// at a time).  *root_at: where the 8 root words are (inside a or b).
+int reduce_to_root(nx_ctx* ctx, u32* a, u32* b, uint32_t max_log, const std::vector<const uint32_t*>& sorted, const std::vector<uint32_t>& logs, const u32** root_at) {
+    u32 *cur = a, *other = b;
+    size_t ci = 0;
+    const size_t n = sorted.size();
+    uint32_t log = max_log;                      // `cur` holds layer `log`
+    KTimer timer(ctx, NX_T_MERKLE, (uint64_t)40 << max_log);
+    while (log > 0) {
+        if (ci < n && logs[ci] == log - 1) {     // the layer above injects columns: node = H(children, column values)
+            const size_t c0 = ci;
+            while (ci < n && logs[ci] == log - 1) ci++;
+            ColSet cs;
+            NX_TRY(make_colset(ctx, (const uint32_t* const*)(sorted.data() + c0), (uint32_t)(ci - c0), &cs));
+            NX_TRY(merkle_layer(ctx, cs, (uint32_t)(ci - c0), cur, other, log - 1));
+            log -= 1;
+        } else {
+            const uint32_t stop = ci < n ? logs[ci] + 1 : 0;          // lowest layer the node-only run may produce
+            const int levels = (int)std::min<uint32_t>(3, log - stop);
+            NX_TRY(merkle_reduce(ctx, cur, other, log, levels));
+            log -= (uint32_t)levels;
+        }
+        std::swap(cur, other);
+    }
+    if (ci != n) return set_err(ctx, NX_ERR_ARG, "reduce_to_root: a column larger than the leaf layer");
+    *root_at = cur;
+    return NX_OK;
+}
+
 int merkle_layer(nx_ctx* ctx, ColSet cols, u32 n_cols, const u32* prev, u32* out, u32 log) {
     u32 n = 1u << log;
     dim3 grid((n + 255) / 256), block(256);
@@ -905,6 +995,119 @@ int nx_merkle_commit(nx_ctx* ctx, const uint32_t* const* d_cols, const uint32_t*
     return NX_OK;
 }
 
+
+// The root of TreeBuilder::extend_evals + commit without the tree (see include/nexus_hip.h).  Streams: the transforms run on the context's
+// stream (and the FFT's side streams, joined back into it); the leaf chain runs on a stream of its own so that chunk c is hashed while
+// chunk c + 1 transforms — ev_lde[s]: slot s holds a finished chunk, ev_hash[s]: slot s has been absorbed and may be overwritten.
+namespace {
+constexpr uint32_t ROOT_CHUNK = 16, ROOT_RING = 2;
+struct RootPipe {
+    nx_ctx* ctx; hipStream_t hash = nullptr; hipEvent_t ev_lde[ROOT_RING] = {}, ev_hash[ROOT_RING] = {};
+    std::vector<void*> bufs;
+    explicit RootPipe(nx_ctx* c) : ctx(c) {}
+    int init() {
+        NX_HIP(ctx, hipStreamCreateWithFlags(&hash, hipStreamNonBlocking));
+        for (uint32_t s = 0; s < ROOT_RING; s++) {
+            NX_HIP(ctx, hipEventCreateWithFlags(&ev_lde[s], hipEventDisableTiming));
+            NX_HIP(ctx, hipEventCreateWithFlags(&ev_hash[s], hipEventDisableTiming));
+        }
+        return NX_OK;
+    }
+    int alloc(size_t words, uint32_t** out) { void* p = nullptr; NX_TRY(dev_alloc(ctx, words * 4, &p)); bufs.push_back(p); *out = (uint32_t*)p; return NX_OK; }
+    ~RootPipe() {      // nothing is handed back to the allocator while either stream may still touch it
+        if (hash) (void)hipStreamSynchronize(hash);
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void* p : bufs) dev_free(ctx, p);
+        for (uint32_t s = 0; s < ROOT_RING; s++) { if (ev_lde[s]) (void)hipEventDestroy(ev_lde[s]); if (ev_hash[s]) (void)hipEventDestroy(ev_hash[s]); }
+        if (hash) (void)hipStreamDestroy(hash);
+    }
+};
+}  // namespace
+
+int nx_commit_root(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, const uint32_t* log_sizes, uint32_t n_cols, uint32_t log_blowup,
+                   uint8_t root[32]) {
+    NX_GUARD(ctx);
+    if (!ctx || !root || (n_cols && (!tw || !d_cols || !log_sizes))) return set_err(ctx, NX_ERR_ARG, "nx_commit_root: NULL argument");
+    if (n_cols == 0) {                              // a tree without columns: the hash of nothing
+        nx_tree* t = nullptr;
+        NX_TRY(nx_merkle_commit(ctx, nullptr, nullptr, 0, &t));
+        const int rc = nx_merkle_root(ctx, t, root);
+        nx_tree_destroy(t);
+        return rc;
+    }
+    uint32_t max_log = 0;
+    for (uint32_t i = 0; i < n_cols; i++) {
+        if (!d_cols[i]) return set_err(ctx, NX_ERR_ARG, "nx_commit_root: NULL column");
+        if (log_sizes[i] < 1 || log_sizes[i] > 29) return set_err(ctx, NX_ERR_ARG, "nx_commit_root: column log size outside 1 .. 29");
+        max_log = std::max(max_log, log_sizes[i]);
+    }
+    if (log_blowup < 1 || max_log + log_blowup > 30) return set_err(ctx, NX_ERR_ARG, "nx_commit_root: log_blowup >= 1 and an extension of at most 2^30 rows required");
+    const uint32_t el = max_log + log_blowup;
+    const size_t M = (size_t)1 << el;
+    std::vector<uint32_t*> leaf;                    // the columns of the largest size, commit order
+    for (uint32_t i = 0; i < n_cols; i++) if (log_sizes[i] == max_log) leaf.push_back(d_cols[i]);
+    const uint32_t n_leaf = (uint32_t)leaf.size(), n_chunks = (n_leaf + ROOT_CHUNK - 1) / ROOT_CHUNK;
+    RootPipe rp(ctx);
+    NX_TRY(rp.init());
+
+    // smaller columns: extended whole, one buffer per size, kept until the reduction has passed their layer
+    std::vector<const uint32_t*> small; std::vector<uint32_t> small_logs;      // commit order
+    {
+        std::vector<uint32_t*> ext(n_cols, nullptr);
+        for (uint32_t lg = max_log - 1; lg >= 1; lg--) {
+            std::vector<uint32_t*> in; std::vector<uint32_t> idx;
+            for (uint32_t i = 0; i < n_cols; i++) if (log_sizes[i] == lg) { in.push_back(d_cols[i]); idx.push_back(i); }
+            if (!in.empty()) {
+                uint32_t* buf = nullptr;
+                NX_TRY(rp.alloc(in.size() << (lg + log_blowup), &buf));
+                std::vector<uint32_t*> out(in.size());
+                for (size_t k = 0; k < in.size(); k++) { out[k] = buf + (k << (lg + log_blowup)); ext[idx[k]] = out[k]; }
+                NX_TRY(nx_lde_batch(ctx, tw, in.data(), (uint32_t)in.size(), lg, log_blowup, out.data()));
+            }
+        }
+        std::vector<uint32_t> order;
+        for (uint32_t i = 0; i < n_cols; i++) if (log_sizes[i] != max_log) order.push_back(i);
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return log_sizes[a] > log_sizes[b]; });      // MerkleProver::commit's order
+        for (uint32_t i : order) { small.push_back(ext[i]); small_logs.push_back(log_sizes[i] + log_blowup); }
+    }
+
+    uint32_t *state = nullptr, *scratch = nullptr, *ring[ROOT_RING] = {nullptr, nullptr};
+    const uint32_t slot_cols = std::min(ROOT_CHUNK, n_leaf), n_slots = std::min(ROOT_RING, n_chunks);
+    NX_TRY(rp.alloc(M * 8, &state));
+    NX_TRY(rp.alloc(root_scratch_nodes(el, small_logs) * 8, &scratch));
+    for (uint32_t s = 0; s < n_slots; s++) NX_TRY(rp.alloc((size_t)slot_cols * M, &ring[s]));
+
+    for (uint32_t c = 0; c < n_chunks; c++) {
+        const uint32_t s = c % ROOT_RING, c0 = c * ROOT_CHUNK, nb = std::min(ROOT_CHUNK, n_leaf - c0);
+        if (c >= ROOT_RING) NX_HIP(ctx, hipStreamWaitEvent(ctx->stream, rp.ev_hash[s], 0));         // the slot's previous chunk has been absorbed
+        std::vector<uint32_t*> out(nb);
+        for (uint32_t k = 0; k < nb; k++) out[k] = ring[s] + (size_t)k * M;
+        NX_TRY(nx_lde_batch(ctx, tw, leaf.data() + c0, nb, max_log, log_blowup, out.data()));       // K3 + K4 of this chunk
+        NX_HIP(ctx, hipEventRecord(rp.ev_lde[s], ctx->stream));
+        NX_HIP(ctx, hipStreamWaitEvent(rp.hash, rp.ev_lde[s], 0));
+        ColSet cs; cs.base = ring[s]; cs.stride = M; cs.table = nullptr;
+        hipStream_t main_stream = ctx->stream;
+        ctx->stream = rp.hash;                                                                       // the leaf chain launches on the context's stream: lend it the hash stream
+        const int rc = leaf_chain_launch(ctx, cs, nb, c0, n_leaf, c ? state : nullptr, state, 0, (uint64_t)M);
+        ctx->stream = main_stream;
+        NX_TRY(rc);
+        NX_HIP(ctx, hipEventRecord(rp.ev_hash[s], rp.hash));
+    }
+    NX_HIP(ctx, hipStreamWaitEvent(ctx->stream, rp.ev_hash[(n_chunks - 1) % ROOT_RING], 0));        // the chain is sequential: the last chunk's event covers all
+    const uint32_t* root_at = nullptr;
+    NX_TRY(reduce_to_root(ctx, state, scratch, el, small, small_logs, &root_at));
+    return nx_download(ctx, (uint32_t*)root, root_at, 8);
+}
+
+int nx_verifier_tree_commit_columns(nx_verifier* verifier, nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, const uint32_t* log_sizes, uint32_t n_cols,
+                                    uint8_t root[32]) {
+    NX_GUARD(ctx);
+    if (!verifier || !ctx || !root) return set_err(ctx, NX_ERR_ARG, "nx_verifier_tree_commit_columns: NULL argument");
+    if (ctx->hash_mode != verifier->s.cfg.hash_mode) return set_err(ctx, NX_ERR_ARG, "nx_verifier_tree_commit_columns: the context's hash mode is not the verifier's");
+    NX_TRY(nx_commit_root(ctx, tw, d_cols, log_sizes, n_cols, verifier->s.cfg.log_blowup, root));
+    const int rc = nx_verifier_tree_commit(verifier, root, log_sizes, n_cols);
+    return rc == NX_OK ? NX_OK : set_err(ctx, rc, std::string("nx_verifier_tree_commit_columns: ") + nx_verifier_last_error(verifier));
+}
 
 int nx_merkle_leaf_chain(nx_ctx* ctx, const uint32_t* const* d_cols, uint32_t n_cols, uint32_t log_size, uint32_t col_offset,
                          uint32_t total_cols, const uint32_t* d_state_in, uint32_t* d_state_out, uint64_t row_begin, uint64_t n_rows) {

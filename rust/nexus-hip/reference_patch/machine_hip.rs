@@ -46,6 +46,7 @@ use nexus_hip::record::{record_component, TraceLocations};
 // the steps both reference patches share (this one and prove2_hip.rs): rust/nexus-hip/src/simd_host.rs
 use nexus_hip::simd_host::{columns_read_by_fractions, commit_tree_keeping_evaluations, host_channel_at, interaction_tree_on_device, pcs_config, secure_from_words, SimdEval};
 use nexus_hip::{proof_bytes, HipError, RecordedComponent, Session};
+use nexus_hip::verify_words;
 
 fn to_proving_error(e: HipError) -> ProvingError {
     match e {
@@ -190,10 +191,26 @@ impl<C: MachineChip + Sync> Machine<C> {
 
         // ---- machine.rs:286-296: stwo::prover::prove on the device; the reference's Proof from its postcard bytes
         let words = session.prove(&components).map_err(to_proving_error)?;
+        // ---- machine.rs:363-500 (`verify`) on the library's own verifier, host only, before the proof leaves a debug build: the transcript
+        // prefix replayed from the proof's roots, the same recorded components, core::verifier::verify (nx_verifier_*).  A release
+        // caller runs the same call wherever it would call `nexus_vm_prover::verify` on bytes of this prover (`verify_hip_words` below).
+        if cfg!(debug_assertions) {
+            Self::verify_hip_words(view, &all_log_sizes, &claimed_words, &components, &words).expect("the device proof fails the library's verifier");
+        }
         let bytes = proof_bytes(&words, &claimed_words, &all_log_sizes).map_err(to_proving_error)?;
         let proof: Proof = postcard::from_bytes(&bytes).expect("nx_proof_serialize_stwo emits the serde layout of machine::Proof");
         debug_assert!(proof.claimed_sum == all_claimed_sums && proof.log_size == all_log_sizes);
         debug_assert!(INTERACTION_TRACE_IDX == 2 && SecureField::zero().is_zero());
         Ok(proof)
+    }
+
+    /// `Machine::verify_with_extensions` (machine.rs:299-485) for the NXP1 words of `prove_hip*`: what the reference's verifier does after
+    /// its preprocessed-root comparison (:363-417 — `nexus_hip::simd_host::preprocessed_root_on_device` against root 0 of the proof), on
+    /// the library's host verifier.  `components`: recorded as for the prove, from the lookup elements the verifier drew (:451) and the
+    /// proof's claimed sums.
+    pub fn verify_hip_words(view: &View, all_log_sizes: &[u32], claimed_words: &[u32], components: &[RecordedComponent], words: &[u32]) -> Result<(), HipError> {
+        let mut prefix: Vec<u64> = view.view_associated_data().unwrap_or_default().into_iter().map(u64::from).collect();
+        prefix.extend(all_log_sizes.iter().map(|&l| l as u64));
+        verify_words(&pcs_config(&PcsConfig::default(), LOG_CONSTRAINT_DEGREE), &prefix, claimed_words, components, words)
     }
 }

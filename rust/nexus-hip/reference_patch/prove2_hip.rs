@@ -42,6 +42,7 @@ use nexus_hip::record::TraceLocations;
 // the steps both reference patches share (this one and machine_hip.rs): rust/nexus-hip/src/simd_host.rs
 use nexus_hip::simd_host::{columns_read_by_fractions, commit_tree_keeping_evaluations, host_channel_at, interaction_tree_on_device, pcs_config, secure_from_words, SimdEval};
 use nexus_hip::{proof_bytes, HipError, RecordedComponent, Session};
+use nexus_hip::verify_words;
 
 fn to_proving_error(e: HipError) -> ProvingError {
     match e {
@@ -136,6 +137,13 @@ pub fn prove_hip(trace: &impl Trace, view: &View) -> Result<Proof, ProvingError>
 
     // ---- prove.rs:123-133: stwo::prover::prove on the device; the reference's Proof from its postcard bytes
     let words = session.prove(&recorded).map_err(to_proving_error)?;
+    // ---- verify.rs:28-143 (`verify`) on the library's own verifier, host only, before the proof leaves a debug build: the transcript
+    // prefix replayed from the proof's roots, the same recorded components, core::verifier::verify (nx_verifier_*)
+    if cfg!(debug_assertions) {
+        let mut prefix: Vec<u64> = view.view_associated_data().unwrap_or_default().into_iter().map(u64::from).collect();
+        prefix.extend(log_sizes.iter().map(|&l| l as u64));
+        verify_words(&cfg, &prefix, &claimed_words, &recorded, &words).expect("the device proof fails the library's verifier");
+    }
     let bytes = proof_bytes(&words, &claimed_words, &log_sizes).map_err(to_proving_error)?;
     let proof: Proof = postcard::from_bytes(&bytes).expect("nx_proof_serialize_stwo emits the serde layout of prove::Proof");
     debug_assert!(proof.claimed_sums == claimed_sums && proof.log_sizes == log_sizes);

@@ -63,6 +63,8 @@ pub enum HipError {
     ConstraintsNotSatisfied,
     Argument(String),
     Device(i32, String),
+    /// `VerificationError` (NX_ERR_VERIFY): a well-formed proof failed the named check of `Verifier::verify`
+    Verification(String),
 }
 
 pub(crate) fn try_check(c: *const sys::nx_ctx, rc: i32) -> Result<(), HipError> {
@@ -427,13 +429,7 @@ impl Session {
     }
     /// stwo::prover::prove (machine.rs:286-290): NXP1 proof words
     pub fn prove(&mut self, comps: &[RecordedComponent]) -> Result<Vec<u32>, HipError> {
-        let raw: Vec<sys::nx_air_component> = comps.iter().map(|c| sys::nx_air_component {
-            log_size: c.log_size, program: c.program.as_ptr(), n_instr: c.program.len() as u32, n_regs: c.n_regs,
-            econsts: c.econsts.as_ptr(), n_econsts: (c.econsts.len() / 4) as u32, n_constraints: c.n_constraints,
-            col_tree: c.col_tree.as_ptr(), col_index: c.col_index.as_ptr(), n_cols: c.col_tree.len() as u32,
-            mask_count: c.mask_count.as_ptr(), mask_offsets: c.mask_offsets.as_ptr(), kernel: std::ptr::null(),
-            log_constraint_degree_bound: c.log_constraint_degree_bound,
-        }).collect();
+        let raw = raw_components(comps);
         let (mut words, mut n) = (std::ptr::null_mut(), 0usize);
         try_check(self.ctx, unsafe { sys::nx_prover_prove(self.p, raw.as_ptr(), raw.len() as u32, &mut words, &mut n, std::ptr::null_mut()) })?;
         let v = unsafe { std::slice::from_raw_parts(words, n) }.to_vec();
@@ -448,6 +444,90 @@ impl Session {
         try_check(self.ctx, unsafe { sys::nx_ctx_set_option(self.ctx, c.as_ptr(), value) })
     }
 }
+fn raw_components(comps: &[RecordedComponent]) -> Vec<sys::nx_air_component> {
+    comps.iter().map(|c| sys::nx_air_component {
+        log_size: c.log_size, program: c.program.as_ptr(), n_instr: c.program.len() as u32, n_regs: c.n_regs,
+        econsts: c.econsts.as_ptr(), n_econsts: (c.econsts.len() / 4) as u32, n_constraints: c.n_constraints,
+        col_tree: c.col_tree.as_ptr(), col_index: c.col_index.as_ptr(), n_cols: c.col_tree.len() as u32,
+        mask_count: c.mask_count.as_ptr(), mask_offsets: c.mask_offsets.as_ptr(), kernel: std::ptr::null(),
+        log_constraint_degree_bound: c.log_constraint_degree_bound,
+    }).collect()
+}
+
+/// `nexus_vm_prover::verify` around Stwo (machine.rs:299-485; prover2 verify.rs:28-143) on the library's own verifier: the mirror of
+/// `Session`, call for call — `mix_u64`, `tree_commit` with a ROOT instead of columns, `draw_felts`, `mix_felts`, `verify`.  Host only: no
+/// context, no GPU (include/nexus_hip.h `nx_verifier_*`).  The node-hash rule is `cfg.hash_mode`.
+pub struct Verifier { v: *mut sys::nx_verifier }
+unsafe impl Send for Verifier {}
+impl Verifier {
+    pub fn new(cfg: &sys::nx_pcs_config) -> Result<Self, HipError> {
+        let mut v = std::ptr::null_mut();
+        match unsafe { sys::nx_verifier_create(cfg, cfg.hash_mode as i32, &mut v) } {
+            sys::NX_OK => Ok(Verifier { v }),
+            rc => Err(if rc == sys::NX_ERR_ARG { HipError::Argument("configuration outside the verifier's range".into()) } else { HipError::Device(rc, "nx_verifier_create".into()) }),
+        }
+    }
+    fn text(&self) -> String { unsafe { std::ffi::CStr::from_ptr(sys::nx_verifier_last_error(self.v)) }.to_string_lossy().into_owned() }
+    fn result(&self, rc: i32) -> Result<(), HipError> {
+        match rc {
+            sys::NX_OK => Ok(()),
+            sys::NX_ERR_VERIFY => Err(HipError::Verification(self.text())),
+            sys::NX_ERR_ARG => Err(HipError::Argument(self.text())),
+            _ => Err(HipError::Device(rc, self.text())),
+        }
+    }
+    pub fn mix_u64(&mut self, v: u64) -> Result<(), HipError> { self.result(unsafe { sys::nx_verifier_mix_u64(self.v, v) }) }
+    pub fn mix_felts(&mut self, felts: &[u32]) -> Result<(), HipError> { self.result(unsafe { sys::nx_verifier_mix_felts(self.v, felts.as_ptr(), (felts.len() / 4) as u32) }) }
+    pub fn draw_felts(&mut self, n: u32) -> Result<Vec<u32>, HipError> { let mut v = vec![0u32; 4 * n as usize]; self.result(unsafe { sys::nx_verifier_draw_felts(self.v, n, v.as_mut_ptr()) })?; Ok(v) }
+    pub fn channel_digest(&self) -> [u8; 32] { let mut d = [0u8; 32]; unsafe { sys::nx_verifier_channel_digest(self.v, d.as_mut_ptr()) }; d }
+    /// CommitmentSchemeVerifier::commit (machine.rs:447-482): the tree's root and its columns' trace log sizes
+    pub fn tree_commit(&mut self, root: &[u8; 32], log_sizes: &[u32]) -> Result<(), HipError> {
+        self.result(unsafe { sys::nx_verifier_tree_commit(self.v, root.as_ptr(), log_sizes.as_ptr(), log_sizes.len() as u32) })
+    }
+    /// The same with the root computed on the device from the columns — the verifier's re-commit of the preprocessed trace
+    /// (machine.rs:363-417; verify.rs:103-143) by `nx_commit_root`: neither the extension nor the tree is kept.  Consumes the columns.
+    pub fn tree_commit_columns(&mut self, session: &Session, tw: &HipTwiddles, cols: &[*mut u32], log_sizes: &[u32]) -> Result<[u8; 32], HipError> {
+        let mut root = [0u8; 32];
+        let rc = unsafe { sys::nx_verifier_tree_commit_columns(self.v, session.ctx(), tw.0, cols.as_ptr(), log_sizes.as_ptr(), log_sizes.len() as u32, root.as_mut_ptr()) };
+        if rc != sys::NX_OK && self.text().is_empty() { return try_check(session.ctx(), rc).map(|_| root); }
+        self.result(rc).map(|_| root)
+    }
+    /// core::verifier::verify (machine.rs:483-485) of NXP1 proof words against the committed roots
+    pub fn verify(&mut self, comps: &[RecordedComponent], words: &[u32]) -> Result<(), HipError> {
+        let raw = raw_components(comps);
+        self.result(unsafe { sys::nx_verifier_verify(self.v, raw.as_ptr(), raw.len() as u32, words.as_ptr(), words.len()) })
+    }
+}
+impl Drop for Verifier { fn drop(&mut self) { unsafe { sys::nx_verifier_destroy(self.v) } } }
+
+/// `nexus_vm_prover::verify` (machine.rs:363-500; prover2 verify.rs:28-160) of the NXP1 words a `Session::prove` returned, for a
+/// statement of the reference's shape — three trace trees, claimed sums mixed before the interaction tree: `prefix` is what the prover
+/// mixed before its first tree (AD bytes, log sizes), the three trace roots enter the transcript from the proof itself, the lookup
+/// elements are draws (they leave the digest where it is: `simd_host::host_channel_at`), `comps` are the components as recorded for the
+/// prove (their lookup elements and claimed-sum shifts included).  Host only.  A caller that holds the preprocessed columns compares
+/// root 0 with `Verifier::tree_commit_columns` / `simd_host::preprocessed_root_on_device` as the reference does.
+pub fn verify_words(cfg: &sys::nx_pcs_config, prefix: &[u64], claimed_words: &[u32], comps: &[RecordedComponent], words: &[u32]) -> Result<(), HipError> {
+    // NXP1: five header words, the commitment count, the roots
+    if words.len() < 6 + 32 || words[5] != 4 { return Err(HipError::Verification("proof shape: four commitments expected".into())); }
+    let root = |t: usize| -> [u8; 32] { let mut r = [0u8; 32]; for k in 0..8 { r[4 * k..4 * k + 4].copy_from_slice(&words[6 + 8 * t + k].to_le_bytes()); } r };
+    let mut logs: [Vec<u32>; 3] = Default::default();
+    for c in comps {
+        for (&t, &i) in c.col_tree.iter().zip(&c.col_index) {
+            if t > 2 { return Err(HipError::Argument("a component column outside the three trace trees".into())); }
+            let l = &mut logs[t as usize];
+            if l.len() <= i as usize { l.resize(i as usize + 1, 0); }
+            l[i as usize] = c.log_size;
+        }
+    }
+    let mut v = Verifier::new(cfg)?;
+    for &x in prefix { v.mix_u64(x)?; }
+    v.tree_commit(&root(0), &logs[0])?;
+    v.tree_commit(&root(1), &logs[1])?;
+    v.mix_felts(claimed_words)?;
+    v.tree_commit(&root(2), &logs[2])?;
+    v.verify(comps, words)
+}
+
 impl RecordedComponent {
     /// An upper bound of every constraint's degree in the trace columns: the smallest sound `log_constraint_degree_bound` is the e with
     /// max degree <= 2^e + 1 (what a `FrameworkEval::max_constraint_log_degree_bound` must return, components/mod.rs:44-45).
