@@ -8,7 +8,11 @@
  * "bad" it corrupts one trace cell first and expects NX_ERR_PROTOCOL (ProvingError::ConstraintsNotSatisfied).
  * The proof is then checked by the verifier session (nx_verifier_*: host only, no context) with the same transcript prefix, the three
  * roots the prover returned and the same component: "verified: accepted", and, with one word of the proof flipped,
- * "verified: refused (<the failing check>)". */
+ * "verified: refused (<the failing check>)".
+ * With the argument "check" ("session_prove check", "session_prove bad check") the trace checker runs before the prove
+ * (nx_prover_check: every constraint on every row of the trace domain) and prints "check: ok" or, per failing constraint,
+ * "check: component 0 constraint 0: 1 row(s), first at row 15, value 1" — the constraint and the natural trace row the prover's
+ * one-sentence refusal cannot name (storage position 7 of the bit-reversed circle-domain order holds row 15). */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -18,7 +22,8 @@
 #define CHECK(call) do { int rc_ = (call); if (rc_ != NX_OK) { fprintf(stderr, "%s failed (%d): %s\n", #call, rc_, nx_last_error(ctx)); return 1; } } while (0)
 
 int main(int argc, char** argv) {
-    const int bad = argc > 1 && !strcmp(argv[1], "bad");
+    int bad = 0, check = 0;
+    for (int k = 1; k < argc; k++) { bad |= !strcmp(argv[k], "bad"); check |= !strcmp(argv[k], "check"); }
     const uint32_t log = 6, n = 1u << 6;
     nx_ctx* ctx = NULL;
     if (nx_ctx_create(0, &ctx) != NX_OK) { fprintf(stderr, "nx_ctx_create: %s\n", nx_last_error(NULL)); return 2; }
@@ -62,6 +67,17 @@ int main(int argc, char** argv) {
     memset(&comp, 0, sizeof comp);
     comp.log_size = log; comp.program = prog; comp.n_instr = sizeof prog / sizeof prog[0]; comp.n_regs = 5; comp.n_constraints = 1;
     comp.col_tree = col_tree; comp.col_index = col_index; comp.n_cols = 4; comp.mask_count = mask_count; comp.mask_offsets = mask_offsets;
+
+    if (check) {
+        nx_check_failure fl[4];
+        uint32_t n_failed = 0;
+        const int crc = nx_prover_check(pr, &comp, 1, fl, 4, &n_failed);
+        if (crc != NX_OK && crc != NX_ERR_PROTOCOL) { fprintf(stderr, "nx_prover_check failed (%d): %s\n", crc, nx_last_error(ctx)); return 1; }
+        if (!n_failed) printf("check: ok\n");
+        for (uint32_t k = 0; k < n_failed && k < 4; k++)
+            printf("check: component %u constraint %u: %llu row(s), first at row %u, value %u\n", (unsigned)fl[k].component, (unsigned)fl[k].constraint,
+                   (unsigned long long)fl[k].n_rows, (unsigned)fl[k].first_row, (unsigned)fl[k].value[0]);
+    }
 
     uint32_t* proof = NULL; size_t n_words = 0;
     int rc = nx_prover_prove(pr, &comp, 1, &proof, &n_words, NULL);

@@ -81,7 +81,9 @@ int nx_ctx_set_hash_mode(nx_ctx* ctx, int mode);
  * (highest level built by the fused sub-tree launch; 0 = one launch per level), "merkle.top" (the level, 1..10, from which ONE block
  * builds the rest of a tree), "merkle.pair_levels" (two node-only levels per launch
  * above it), "fri.device_channel", "fri.tail" (0 = off, 1 = the FRI layers of <= 2^11 points in one launch,
- * 2..11 = from 2^that many points), "logup.scan_tiled", "logup.per_column".  "host.pack_threads" (1..64; default
+ * 2..11 = from 2^that many points), "logup.scan_tiled", "logup.per_column", "merkle.fused" (0 = off, else the smallest log size from which a tree of <= 4 columns of one
+ * size gets its leaf hash and 6 levels in one launch), "machine.logup_program" (1: nx_prove_machine builds every wide-tuple component's interaction
+ * trace through nx_logup_program).  "host.pack_threads" (1..64; default
  * min(16, hardware threads)): host threads that pack NX_COL_U32_AS_U16 / NX_COL_U32_AS_U8 columns of the narrow upload entry points.
  * Unknown names and out-of-range values are NX_ERR_ARG.
  * None of them changes a result: proofs, roots and transforms are bit-identical under every setting. */
@@ -646,6 +648,50 @@ typedef struct {
  * (and a failed call restores it at once), so proving the committed statement again — or retrying — gives the same bytes. */
 int nx_prover_prove(nx_prover* prover, const nx_air_component* components, uint32_t n_components, uint32_t** proof_words,
                     size_t* n_words, nx_prove_stats* stats);
+
+/* ------------------------------------------- the trace checker: stwo_constraint_framework::assert_constraints_on_polys on the device
+ * The reference's day-to-day tool for the author of an AIR or of a trace (prover/src/test_utils.rs:113-168 assert_chip, the tests of
+ * every prover2 component): every constraint on every row of the TRACE domain, and the first one that is not zero named.  nx_prover_prove
+ * can only say ConstraintsNotSatisfied — by then all constraints of all components are folded into one random linear combination.
+ * SEMANTICS.  Domain: CanonicCoset(log_size).circle_domain() of the component, i.e. the 2^log_size rows the caller filled (not the
+ * committed extension, which does not contain them).  Rows in every report are NATURAL trace rows i (coset order, the VM step), not
+ * storage positions: position pos of the bit-reversed circle-domain order holds row d < N/2 ? 2d : 2N-1-2d with d = bitrev(pos).  A LOAD /
+ * LOADE with offset o at row i reads row (i + o) mod N.  A base-field constraint fails at a row where it is not 0, a secure one where
+ * any of its four coordinates is not 0.  The logup claimed-sum consistency is part of the recorded program (the [-1, 0] constraint).
+ * Per failing constraint: how many rows fail, the smallest such row, the constraint's value there.  The counts are integers combined
+ * with add and min: the report is the same on every run, whatever the scheduling. */
+typedef struct nx_check_failure {
+    uint32_t component, constraint;   /* index into the component array; ordinal of the add_constraint */
+    uint32_t first_row;               /* smallest natural trace row at which it is not zero            */
+    uint32_t value[4];                /* its value there (a base-field constraint: value[1..3] = 0)    */
+    uint64_t n_rows;                  /* rows at which it is not zero                                  */
+} nx_check_failure;
+/* The primitive: one recorded program over d_cols, TRACE-DOMAIN EVALUATIONS (bit-reversed circle-domain order, 2^log_size words each —
+ * what nx_prover_tree_begin hands out, before the commit; columns no constraint loads may be NULL).  Writes min(cap, failing) entries
+ * in ascending constraint order (component = 0) and the number of failing constraints to *n_failed.  The program's check kernels are
+ * compiled by hiprtc on first use and kept per context, keyed by the program bytes (nx_air_cache_dir applies).  A valid trace costs
+ * one pass over the loaded columns: no atomic, nothing stored to memory (failing rows are reduced per wave, then per block in LDS,
+ * then one atomic pair per block and failing constraint).  Blocking.
+ * Returns NX_OK when every constraint holds on every row; NX_ERR_PROTOCOL when at least one fails — nx_last_error then names the first
+ * one, "component 0 constraint 2: not zero on 1 of 64 rows, first at row 47" — with the array and the count filled in both cases; any
+ * other code is an ordinary error and leaves them untouched.
+ * nx_air_check_source: the HIP source of those kernels (host only, no context, no GPU; free with nx_free_host). */
+int nx_air_check(nx_ctx* ctx, const struct nx_cinstr* program, uint32_t n_instr, uint32_t n_regs, const uint32_t* const* d_cols,
+                 uint32_t n_cols, const uint32_t* econsts, uint32_t n_econsts, uint32_t n_constraints, uint32_t log_size,
+                 nx_check_failure* failures, uint32_t cap, uint32_t* n_failed);
+int nx_air_check_source(const struct nx_cinstr* program, uint32_t n_instr, uint32_t n_regs, uint32_t n_cols, uint32_t n_econsts,
+                        uint32_t n_constraints, char** h_source_out);
+/* The session form: the component array of nx_prover_prove, once the trees the components name are committed; any number of times,
+ * before or after nx_prover_prove.  Reads the session only: the transcript (nx_prover_channel_digest) and the proof a later
+ * nx_prover_prove returns are unchanged.  The committed columns hold coefficients, so the columns a component's constraints load are
+ * evaluated on its trace domain into scratch, checked, and freed before the next component.  Entries in (component, constraint) order.
+ * DEVICE MEMORY: peak above the session's  <=  4 * 2^log_size * (columns the constraints load)  of the largest component, plus
+ * 24 bytes per column and constraint for the tables and, on the failing path only, 20 bytes per loaded word of every distinct
+ * reported first row (value[] is computed on the host from those words); each term rounded up to 256.  Nothing is kept afterwards.
+ * Statement errors (a column claimed by no component, a LOAD offset missing from the mask, a column outside the committed trees ...)
+ * are NX_ERR_ARG with nx_prover_prove's texts.  A session with a communicator is refused (NX_ERR_ARG, "one GPU").  Returns as nx_air_check. */
+int nx_prover_check(nx_prover* prover, const nx_air_component* components, uint32_t n_components, nx_check_failure* failures,
+                    uint32_t cap, uint32_t* n_failed);
 
 /* ------------------------------------------- the verifier session: core::verifier::verify over recorded AIRs
  * `nexus_vm_prover::verify` (reference prover/src/lib.rs:26-33; prover/src/machine.rs:299-485; prover2/machine/src/verify.rs:28-143)

@@ -8,6 +8,7 @@ synthetic-machine `prove`.  There is NO CPU fallback: importing works without a 
 table can be checked), but creating a `HipBackend` raises if libnexus_hip.so or a gfx950 device is
 missing.
 """
+import collections
 import ctypes as C
 import os
 
@@ -186,6 +187,51 @@ def logup_program_source(program, n_cols, n_logup_cols):
     out = src.value.decode()
     L.nx_free_host(src)
     return out
+
+
+def air_check_source(program, n_cols):
+    """The HIP source of the check kernels nx_air_check compiles for a recorded program (needs no GPU and no context)."""
+    L = load_library()
+    ins = _u32(program.instrs).reshape(-1)
+    n_c = int(sum(1 for op in ins[0::4] if op in (13, 14)))
+    src = C.c_void_p()
+    rc = L.nx_air_check_source(ins.ctypes.data_as(C.c_void_p), len(ins) // 4, program.n_regs, n_cols, len(_u32(program.econsts).reshape(-1)) // 4, n_c, C.byref(src))
+    if rc != 0:
+        raise NexusHipError(f"nx_air_check_source failed ({rc}): {L.nx_last_error(None).decode()}")
+    try:
+        return C.string_at(src.value).decode()
+    finally:
+        L.nx_free_host(src)
+
+
+class CheckFailureC(C.Structure):
+    _fields_ = [("component", C.c_uint32), ("constraint", C.c_uint32), ("first_row", C.c_uint32), ("value", C.c_uint32 * 4), ("n_rows", C.c_uint64)]
+
+
+class CheckFailure(collections.namedtuple("CheckFailure", "component constraint first_row value n_rows")):
+    """One failing constraint of a trace check (nx_check_failure): first_row is a natural trace row, value a 4-tuple."""
+
+
+class CheckReport:
+    """What nx_air_check / nx_prover_check found: ok, n_failed (all failing constraints), failures (the first max_failures of them, in
+    (component, constraint) order) and message (nx_last_error's sentence about the first one, "" when ok)."""
+
+    def __init__(self, n_failed, failures, message):
+        self.n_failed, self.failures, self.message = n_failed, failures, message
+        self.ok = n_failed == 0
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return f"CheckReport(ok={self.ok}, n_failed={self.n_failed}, failures={self.failures!r})"
+
+
+def _check_report(be, rc, arr, n_failed, cap):
+    if rc not in (0, -4):        # NX_OK / NX_ERR_PROTOCOL: both carry a report
+        be._chk(rc)
+    fl = [CheckFailure(int(f.component), int(f.constraint), int(f.first_row), tuple(int(v) for v in f.value), int(f.n_rows)) for f in arr[:min(cap, n_failed.value)]]
+    return CheckReport(int(n_failed.value), fl, be.L.nx_last_error(be.ctx).decode() if rc else "")
 
 
 def air_constraint_degrees(program, n_cols):
@@ -399,6 +445,15 @@ class ProverSession:
         out = np.ctypeslib.as_array(words, shape=(n.value,)).copy()
         self.be.L.nx_free_host(words)
         return (out, stats.as_dict()) if want_stats else out
+
+    def check(self, components, max_failures=64):
+        """nx_prover_check: every recorded constraint of every component on every row of its trace domain (the committed trees); a
+        CheckReport instead of an exception when constraints fail.  Leaves the transcript and later proofs alone."""
+        arr, keep = _air_components(components)
+        out = (CheckFailureC * max(1, max_failures))()
+        n = C.c_uint32(0)
+        rc = self.be.L.nx_prover_check(self.h, arr, len(components), out, int(max_failures), C.byref(n))
+        return _check_report(self.be, rc, out, n, max_failures)
 
     def close(self):
         if self.h and self.be.ctx:
@@ -1061,6 +1116,18 @@ class HipBackend:
                                                     ec.ctypes.data_as(C.c_void_p), len(ec) // 4, pw.ctypes.data_as(C.c_void_p), len(pw) // 4,
                                                     den.ctypes.data_as(C.c_void_p), log_size, log_eval, acc4.col_ptrs()))
         return acc4
+
+    def air_check(self, program, column_ptrs, log_size, max_failures=64, econsts=None):
+        """nx_air_check: every constraint of an air_program.Program on every row of the trace domain.  column_ptrs: device addresses
+        (ints; None for columns no constraint loads) of trace-domain evaluations.  Returns a CheckReport."""
+        ins = _u32(program.instrs).reshape(-1)
+        ptrs = (C.c_void_p * max(1, len(column_ptrs)))(*column_ptrs)
+        ec = _u32(program.econsts if econsts is None else econsts).reshape(-1)
+        out = (CheckFailureC * max(1, max_failures))()
+        n = C.c_uint32(0)
+        rc = self.L.nx_air_check(self.ctx, ins.ctypes.data_as(C.c_void_p), len(ins) // 4, program.n_regs, ptrs, len(column_ptrs),
+                                 ec.ctypes.data_as(C.c_void_p) if len(ec) else None, len(ec) // 4, program.n_constraints, log_size, out, int(max_failures), C.byref(n))
+        return _check_report(self, rc, out, n, max_failures)
 
     def prover_session(self, cfg, max_log_size):
         return ProverSession(self, cfg, max_log_size)

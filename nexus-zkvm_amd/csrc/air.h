@@ -36,5 +36,10 @@ void air_kernel_shape(const nx_air_kernel* k, uint32_t* n_cols, uint32_t* n_econ
 void air_constraint_degrees(const nx_cinstr* prog, uint32_t n_instr, uint32_t n_regs, std::vector<uint32_t>* out);
 void air_constraint_neighbours(const nx_cinstr* prog, uint32_t n_instr, uint32_t n_regs, std::vector<char>* out);   // per constraint: reads a column at a non-zero row offset
 void air_subset_columns(const nx_cinstr* prog, uint32_t n_instr, uint32_t n_regs, uint32_t n_cols, const uint8_t* select, std::vector<char>* used);
+// the trace checker (air_jit.hip): one component's failing constraints appended to *out (value[] for the first n_values of them); the report of both entry points
+int air_check_component(nx_ctx* ctx, const char* who, const nx_cinstr* program, uint32_t n_instr, uint32_t n_regs, const uint32_t* const* d_cols, uint32_t n_cols,
+                        const uint32_t* econsts, uint32_t n_econsts, uint32_t n_constraints, uint32_t log_size, uint32_t component, size_t n_values,
+                        std::vector<nx_check_failure>* out);
+int air_check_report(nx_ctx* ctx, const std::vector<nx_check_failure>& all, const std::vector<uint32_t>& comp_log, nx_check_failure* failures, uint32_t cap, uint32_t* n_failed);
 
 }  // namespace nx

@@ -36,7 +36,7 @@ struct nx_air_kernel {
     std::vector<hipModule_t> modules;    // one code object, or one per PART of the program's kernels (compiled side by side in helper processes: compile_parts)
     std::vector<hipFunction_t> fns;      // one kernel per program segment (air_kernel, air_kernel_1, ...), launched back to back
     uint32_t n_cols, n_econsts, n_constraints;
-    uint32_t kind = 0;                    // 0: constraint kernels (nx_air_eval's argument list); 1: fraction kernels of nx_logup_program (another argument list)
+    uint32_t kind = 0;                    // 0: constraint kernels (nx_air_eval's argument list); 1: fraction kernels of nx_logup_program; 2: check kernels of nx_air_check (other argument lists)
     std::vector<char> code;              // the gfx950 code object the module was loaded from, or a container of several (nx_air_kernel_save; the disk cache)
 };
 
@@ -95,6 +95,39 @@ FI u32 row_offset(u32 r, int log_size, int e, int offset) {
     else idx = ((idx - half - step) & (half - 1)) + half;
     return bitrev(idx, e);
 }
+)SRC";
+
+// The TRACE domain (the 2^log_size rows the caller filled, CanonicCoset(log_size).circle_domain() in bit-reversed order): the trace step is
+// +1 in natural coset order and crosses between the two halves of the circle domain, so row_offset above (which needs e > log_size)
+// does not apply.  Shared by the logup fraction kernels and the check kernels.
+static const char* TRACE_ROWS_PRELUDE = R"SRC(
+// natural coset row <-> position in bit-reversed circle-domain order (reference prover/src/trace/utils_external.rs:24-39)
+FI u32 pos_of_coset_row(u32 c, int log) { const u32 N = 1u << log; const u32 d = (c & 1) ? N - 1 - (c >> 1) : (c >> 1); return bitrev(d, log); }
+FI u32 coset_row_of_pos(u32 p, int log) { const u32 N = 1u << log, d = bitrev(p, log); return d < N / 2 ? 2 * d : 2 * (N - 1 - d) + 1; }
+FI u32 trace_row_offset(u32 r, int log, int off) { if (off == 0) return r; return pos_of_coset_row((coset_row_of_pos(r, log) + (u32)off) & ((1u << log) - 1), log); }
+)SRC";
+
+// The reporting path of a check kernel (nx_air_check).  A wave votes; when no lane failed — every wave of a valid trace — nothing else
+// happens: no atomic, nothing stored to memory.  Otherwise the wave's smallest failing natural row is reduced over the 64 lanes (xor
+// butterfly) and lane 0 adds the number of failing lanes to the BLOCK's count of the constraint and takes the minimum into the block's
+// first row, both in LDS; when the block is through, one lane per constraint that failed somewhere in the block carries the pair to
+// count[j] / first[j] in memory: one global atomic pair per block per failing constraint.  (Measured on an MI355X, 2^20 rows, 303
+// constraints failing on every row: 16.9 ms with the waves going to memory themselves, one pair per wave; DESIGN.md section 7b has
+// the figure with this block stage.)  Integers combined with add and min: the result does not depend on the order of waves or blocks.
+// check_report is kept out of line: the straight-line body stays as small as the constraint kernels'.
+static const char* CHECK_PRELUDE = R"SRC(
+typedef __attribute__((address_space(3))) u32 lds_u32;
+__attribute__((device)) __attribute__((noinline)) void check_report(lds_u32* cnt, lds_u32* first, u64 votes, bool failed, u32 row) {
+    const u32 lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    u32 m = failed ? row : 0xffffffffu;
+    for (u32 k = 32; k; k >>= 1) { const u32 o = (u32)__builtin_amdgcn_ds_bpermute((int)((lane ^ k) << 2), (int)m); m = o < m ? o : m; }
+    if (lane == 0) {
+        (void)__hip_atomic_fetch_add(cnt, (u32)__builtin_popcountll(votes), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        (void)__hip_atomic_fetch_min(first, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+#define CHECK(l, cond) { const bool f_ = live && (cond); const u64 v_ = __builtin_amdgcn_ballot_w64(f_); if (v_) check_report(l_cnt + (l), l_first + (l), v_, f_, nat); }
+FI void block_sync() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
 )SRC";
 
 // Straight-line code has no loops, so its size grows with the AIR: the reference-shaped machine with 250 logup columns is > 1 MB of
@@ -214,8 +247,23 @@ struct LazyAcc {
     }
 };
 
-static std::string generate_kernel(const nx_cinstr* prog, const std::vector<uint32_t>& keep, const std::vector<uint32_t>& cons_index, uint32_t n_regs, const std::string& name) {
+// check: the kernel of nx_air_check — one lane per row of the TRACE domain, every selected constraint tested instead of accumulated
+static std::string generate_kernel(const nx_cinstr* prog, const std::vector<uint32_t>& keep, const std::vector<uint32_t>& cons_index, uint32_t n_regs, const std::string& name, bool check = false) {
     std::string s;
+    // check mode: the constraints of this kernel are consecutive (no selection), local index l <-> constraint first_c + l
+    uint32_t first_c = 0, n_local = 0;
+    for (uint32_t i : keep) if (prog[i].op == NX_C_CONSTRAINT_B || prog[i].op == NX_C_CONSTRAINT_E) { if (!n_local) first_c = cons_index[i]; n_local++; }
+    if (check)
+        s += "extern \"C\" __attribute__((global)) __attribute__((amdgpu_flat_work_group_size(256, 256))) void " + name + "(const u32* const* __restrict__ cols, const u32* __restrict__ econst,\n"
+             "    int log_size, u64* count, u32* first, u32 n) {\n"
+             "  const u32 p_ = __builtin_amdgcn_workgroup_id_x() * 256 + __builtin_amdgcn_workitem_id_x();\n"
+             "  const bool live = p_ < n;\n  const u32 r = live ? p_ : 0;\n"       // no early return: every lane of a wave takes part in the votes
+             "  const u32 nat = coset_row_of_pos(r, log_size);\n"
+             "  __attribute__((shared)) u32 l_cnt_[" + std::to_string(std::max(n_local, 1u)) + "]; __attribute__((shared)) u32 l_first_[" + std::to_string(std::max(n_local, 1u)) + "];\n"
+             "  lds_u32* const l_cnt = (lds_u32*)l_cnt_; lds_u32* const l_first = (lds_u32*)l_first_;\n"
+             "  for (u32 t = __builtin_amdgcn_workitem_id_x(); t < " + std::to_string(n_local) + "u; t += 256) { l_cnt[t] = 0; l_first[t] = 0xffffffffu; }\n"
+             "  block_sync();\n";
+    else
     s += "extern \"C\" __attribute__((global)) __attribute__((amdgpu_flat_work_group_size(256, 256))) void " + name + "(const u32* const* __restrict__ cols, const u32* __restrict__ econst, const u32* __restrict__ pw,\n"
          "    const u32* __restrict__ denom_inv, int log_size, int e, u32* a0, u32* a1, u32* a2, u32* a3, u32 row_begin, u32 row_end) {\n"
          "  const u32 r = row_begin + __builtin_amdgcn_workgroup_id_x() * 256 + __builtin_amdgcn_workitem_id_x();\n  if (r >= row_end) return;\n"
@@ -225,7 +273,8 @@ static std::string generate_kernel(const nx_cinstr* prog, const std::vector<uint
     for (uint32_t i : keep)
         if (prog[i].op == NX_C_LOAD || prog[i].op == NX_C_LOADE) { int o = (int)prog[i].b; if (std::find(offs.begin(), offs.end(), o) == offs.end()) offs.push_back(o); }
     auto off_name = [](int o) { return std::string("row_") + (o < 0 ? "m" : "p") + std::to_string(o < 0 ? -o : o); };
-    for (int o : offs) s += "  const u32 " + off_name(o) + " = row_offset(r, log_size, e, " + std::to_string(o) + ");\n";
+    for (int o : offs)
+        s += "  const u32 " + off_name(o) + (check ? " = trace_row_offset(r, log_size, " : " = row_offset(r, log_size, e, ") + std::to_string(o) + ");\n";
     for (uint32_t k = 0; k < n_regs; k++) s += (k % 16 == 0 ? std::string("  u32 ") : std::string(", ")) + "r" + std::to_string(k) + ((k % 16 == 15 || k + 1 == n_regs) ? " = 0;\n" : " = 0");
     auto R = [](uint32_t i) { return "r" + std::to_string(i); };
     auto E = [&](uint32_t i) { return "Q{" + R(i) + ", " + R(i + 1) + ", " + R(i + 2) + ", " + R(i + 3) + "}"; };
@@ -262,6 +311,7 @@ static std::string generate_kernel(const nx_cinstr* prog, const std::vector<uint
             break;
         }
         case NX_C_CONSTRAINT_B: {
+            if (check) { s += "  CHECK(" + std::to_string(cons_index[i] - first_c) + "u, " + R(in.a) + " != 0)\n"; break; }
             std::string b = std::to_string(4 * cons_index[i]);
             s += "  s0 = acc_mad(s0, pw[" + b + "], " + R(in.a) + "); s1 = acc_mad(s1, pw[" + b + " + 1], " + R(in.a) + "); s2 = acc_mad(s2, pw[" + b + " + 2], " + R(in.a) + "); s3 = acc_mad(s3, pw[" + b +
                  " + 3], " + R(in.a) + ");\n";
@@ -269,6 +319,7 @@ static std::string generate_kernel(const nx_cinstr* prog, const std::vector<uint
             break;
         }
         case NX_C_CONSTRAINT_E: {
+            if (check) { s += "  CHECK(" + std::to_string(cons_index[i] - first_c) + "u, (" + R(in.a) + " | " + R(in.a + 1) + " | " + R(in.a + 2) + " | " + R(in.a + 3) + ") != 0)\n"; break; }
             std::string b = std::to_string(4 * cons_index[i]);
             s += "  { const Q t_ = q_mul(Q{pw[" + b + "], pw[" + b + " + 1], pw[" + b + " + 2], pw[" + b + " + 3]}, " + E(in.a) + "); s0 += t_.a; s1 += t_.b; s2 += t_.c; s3 += t_.d; }\n";
             if (++pending == 4) { s += fold; pending = 0; }
@@ -277,6 +328,14 @@ static std::string generate_kernel(const nx_cinstr* prog, const std::vector<uint
         default: break;
         }
     }
+    if (check)
+        return s + "  block_sync();\n"
+                   "  for (u32 t = __builtin_amdgcn_workitem_id_x(); t < " + std::to_string(n_local) + "u; t += 256) {\n"
+                   "    const u32 c = l_cnt[t];\n"
+                   "    if (c) {\n"
+                   "      (void)__hip_atomic_fetch_add(count + " + std::to_string(first_c) + "u + t, (u64)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+                   "      (void)__hip_atomic_fetch_min(first + " + std::to_string(first_c) + "u + t, l_first[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
+                   "    }\n  }\n}\n";
     s += "  const u32 di = denom_inv[r >> log_size];\n"
          "  a0[r] = m_add(a0[r], m_mul(acc_final(s0), di)); a1[r] = m_add(a1[r], m_mul(acc_final(s1), di));\n"
          "  a2[r] = m_add(a2[r], m_mul(acc_final(s2), di)); a3[r] = m_add(a3[r], m_mul(acc_final(s3), di));\n}\n";
@@ -315,11 +374,12 @@ static ProgDeps program_deps(const nx_cinstr* prog, uint32_t n_instr, uint32_t n
 // `select` (one flag per constraint, NULL = all): the kernels evaluate only the selected constraints — same alpha-power indices, same
 // column indices as the whole program, so a component's constraints can be evaluated in parts on different domains (the
 // degree-aware composition of prover.hip) and the parts add up to the whole.
-static std::string generate_air_source(const nx_ctx* ctx, const nx_cinstr* prog, uint32_t n_instr, uint32_t n_regs, uint32_t* n_kernels = nullptr, const uint8_t* select = nullptr) {
+static std::string generate_air_source(const nx_ctx* ctx, const nx_cinstr* prog, uint32_t n_instr, uint32_t n_regs, uint32_t* n_kernels = nullptr, const uint8_t* select = nullptr, bool check = false) {
     const ProgDeps pd = program_deps(prog, n_instr, n_regs);
     const auto& deps = pd.deps; const auto& cons_index = pd.cons_index;
     // segments: consecutive constraints whose slices fit the budget
     std::string s = AIR_PRELUDE;
+    if (check) s += std::string(TRACE_ROWS_PRELUDE) + CHECK_PRELUDE;
     uint32_t n_seg = 0;
     std::vector<char> in_seg(n_instr, 0);
     std::vector<uint32_t> seg_cons;
@@ -338,7 +398,7 @@ static std::string generate_air_source(const nx_ctx* ctx, const nx_cinstr* prog,
     auto flush = [&]() {
         std::vector<uint32_t> keep;
         for (uint32_t i = 0; i < n_instr; i++) if (in_seg[i]) keep.push_back(i);
-        s += generate_kernel(prog, keep, cons_index, n_regs, n_seg == 0 ? std::string("air_kernel") : "air_kernel_" + std::to_string(n_seg));
+        s += generate_kernel(prog, keep, cons_index, n_regs, n_seg == 0 ? std::string("air_kernel") : "air_kernel_" + std::to_string(n_seg), check);
         n_seg++;
         std::fill(in_seg.begin(), in_seg.end(), 0); cost = 0;
     };
@@ -810,7 +870,7 @@ int nx_air_kernel_load(nx_ctx* ctx, const uint8_t* blob, size_t n_bytes, nx_air_
     if (!ctx || !blob || !out) return set_err(ctx, NX_ERR_ARG, "nx_air_kernel_load: NULL argument");
     BlobHeader h;
     if (!blob_ok(blob, n_bytes, &h)) return set_err(ctx, NX_ERR_ARG, "nx_air_kernel_load: not a kernel blob of this library version (magic / size / checksum)");
-    if (h.reserved != 0) return set_err(ctx, NX_ERR_ARG, "nx_air_kernel_load: the blob holds the fraction kernels of nx_logup_program (a cache-directory file), not constraint kernels");
+    if (h.reserved != 0) return set_err(ctx, NX_ERR_ARG, "nx_air_kernel_load: the blob holds the kernels of nx_logup_program or nx_air_check (a cache-directory file), not constraint kernels");
     return load_code(ctx, h, (const char*)blob + sizeof h, out);
 }
 
@@ -889,10 +949,6 @@ FI u32 m_inv(u32 a) {
     const u32 t24 = m_mul(m_sqn(t16, 8), t8), t28 = m_mul(m_sqn(t24, 4), t4), t29 = m_mul(m_sqr(t28), a);
     return m_mul(m_sqn(t29, 2), a);
 }
-// natural coset row <-> position in bit-reversed circle-domain order (reference prover/src/trace/utils_external.rs:24-39)
-FI u32 pos_of_coset_row(u32 c, int log) { const u32 N = 1u << log; const u32 d = (c & 1) ? N - 1 - (c >> 1) : (c >> 1); return bitrev(d, log); }
-FI u32 coset_row_of_pos(u32 p, int log) { const u32 N = 1u << log, d = bitrev(p, log); return d < N / 2 ? 2 * d : 2 * (N - 1 - d) + 1; }
-FI u32 trace_row_offset(u32 r, int log, int off) { if (off == 0) return r; return pos_of_coset_row((coset_row_of_pos(r, log) + (u32)off) & ((1u << log) - 1), log); }
 // the norm part of a QM31 inverse: x^-1 = (a, -b) D^-1, D = a^2 - (2 + i) b^2 in CM31, D^-1 = conj(D) / (D.a^2 + D.b^2)
 )SRC"
 #ifndef NX_Q_MUL_NAIVE
@@ -1052,7 +1108,7 @@ int validate_logup_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_ins
 
 static std::string generate_logup_source(const nx_ctx* ctx, const nx_cinstr* prog, uint32_t n_instr, uint32_t n_regs, uint32_t* n_kernels) {
     const ProgDeps pd = program_deps(prog, n_instr, n_regs);
-    std::string s = std::string(AIR_PRELUDE) + LOGUP_PRELUDE;
+    std::string s = std::string(AIR_PRELUDE) + TRACE_ROWS_PRELUDE + LOGUP_PRELUDE;
     std::vector<char> batch_end(n_instr, 0);
     { int last = -1; for (uint32_t i = 0; i < n_instr; i++) if (prog[i].op == NX_C_FRAC || prog[i].op == NX_C_FRACB) { if (last >= 0 && prog[last].dst != prog[i].dst) batch_end[last] = 1; last = (int)i; } if (last >= 0) batch_end[last] = 1; }
     uint32_t n_seg = 0, cost = 0, first_col = 0;
@@ -1163,3 +1219,178 @@ extern "C" int nx_logup_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t 
     if (e != hipSuccess) return hip_fail(ctx, e, "nx_logup_program", __FILE__, __LINE__);
     return NX_OK;
 }
+
+// ================================================================ the trace checker (nx_air_check / nx_prover_check) ========
+// What stwo_constraint_framework::assert_constraints_on_polys is to the reference's authors (prover/src/test_utils.rs assert_chip,
+// every prover2 component's tests): every recorded constraint on every row of the TRACE domain, and for each one that is not zero
+// there the number of such rows, the first of them (natural trace row) and its value.  The third emission mode of this file: the
+// straight-line body of the constraint kernels with a vote instead of the accumulation (generate_kernel, check = true).
+namespace nx {
+
+// the recorded program at ONE trace row on the host (off the hot path: the rows the device reported): loads[k] is the word of the
+// k-th loaded column word in program order; values: 4 words per constraint
+static void host_run_program(const nx_cinstr* prog, uint32_t n_instr, uint32_t n_regs, const uint32_t* econsts, const uint32_t* loads, std::vector<uint32_t>* values) {
+    std::vector<uint32_t> R(n_regs + 4, 0);
+    auto E = [&](uint32_t i) { return q_load(&R[i]); };
+    size_t next = 0;
+    values->clear();
+    for (uint32_t i = 0; i < n_instr; i++) {
+        const nx_cinstr& in = prog[i];
+        switch (in.op) {
+        case NX_C_LOAD: R[in.dst] = loads[next++]; break;
+        case NX_C_CONST: R[in.dst] = in.a; break;
+        case NX_C_ADD: R[in.dst] = m_add(R[in.a], R[in.b]); break;
+        case NX_C_SUB: R[in.dst] = m_sub(R[in.a], R[in.b]); break;
+        case NX_C_MUL: R[in.dst] = m_mul(R[in.a], R[in.b]); break;
+        case NX_C_NEG: R[in.dst] = m_neg(R[in.a]); break;
+        case NX_C_CONSTE: for (int k = 0; k < 4; k++) R[in.dst + k] = econsts[4 * (size_t)in.a + k]; break;
+        case NX_C_ADDE: { const QM31 v = q_add(E(in.a), E(in.b)); q_store(&R[in.dst], v); break; }
+        case NX_C_SUBE: { const QM31 v = q_sub(E(in.a), E(in.b)); q_store(&R[in.dst], v); break; }
+        case NX_C_MULE: { const QM31 v = q_mul(E(in.a), E(in.b)); q_store(&R[in.dst], v); break; }
+        case NX_C_MULEB: { const QM31 v = q_mul_m(E(in.a), R[in.b]); q_store(&R[in.dst], v); break; }
+        case NX_C_ADDEB: { QM31 v = E(in.a); v.a.a = m_add(v.a.a, R[in.b]); q_store(&R[in.dst], v); break; }
+        case NX_C_LOADE: for (int k = 0; k < 4; k++) R[in.dst + k] = loads[next++]; break;
+        case NX_C_CONSTRAINT_B: values->push_back(R[in.a]); values->push_back(0); values->push_back(0); values->push_back(0); break;
+        case NX_C_CONSTRAINT_E: for (int k = 0; k < 4; k++) values->push_back(R[in.a + k]); break;
+        default: break;
+        }
+    }
+}
+static uint32_t host_pos_of_coset_row(uint32_t c, uint32_t log) { const uint32_t N = 1u << log; const uint32_t d = (c & 1) ? N - 1 - (c >> 1) : (c >> 1); return bitrev(d, (int)log); }
+
+// One component: appends its failing constraints (ascending) to *out, `value` filled for the first n_values of them.  d_cols: trace-domain
+// evaluations, 2^log_size words each (columns no constraint loads may be NULL).  Blocking.
+int air_check_component(nx_ctx* ctx, const char* who, const nx_cinstr* program, uint32_t n_instr, uint32_t n_regs, const uint32_t* const* d_cols, uint32_t n_cols,
+                        const uint32_t* econsts, uint32_t n_econsts, uint32_t n_constraints, uint32_t log_size, uint32_t component, size_t n_values,
+                        std::vector<nx_check_failure>* out) {
+    const std::string name(who);
+    if (!ctx) return set_err(ctx, NX_ERR_ARG, name + ": a context is needed to run");
+    if ((n_instr && !program) || (n_econsts && !econsts) || (n_cols && !d_cols)) return set_err(ctx, NX_ERR_ARG, name + ": NULL argument");
+    if (log_size < 1 || log_size > 30) return set_err(ctx, NX_ERR_ARG, name + ": log_size out of range");
+    uint32_t n_c = 0;
+    NX_TRY(validate_air_program(ctx, program, n_instr, n_regs, n_cols, n_econsts, &n_c));
+    if (n_c != n_constraints) return set_err(ctx, NX_ERR_ARG, name + ": the program adds a different number of constraints than announced");
+    if (n_c == 0) return NX_OK;
+    // only what a constraint depends on is emitted, so only those columns must be there
+    std::vector<char> used;
+    air_subset_columns(program, n_instr, n_regs, n_cols, nullptr, &used);
+    for (uint32_t k = 0; k < n_cols; k++) if (used[k] && !d_cols[k]) return set_err(ctx, NX_ERR_ARG, name + ": the program loads a column that was passed as NULL");
+    // the kernels: per context, keyed by the program bytes (nx_logup_program's cache, another key)
+    std::string key = "check|";
+    key.append((const char*)program, (size_t)n_instr * sizeof(nx_cinstr));
+    key += "|" + std::to_string(n_regs) + "|" + std::to_string(n_cols) + "|" + std::to_string(n_econsts) + "|" + std::to_string(segment_budget(ctx));
+    const nx_air_kernel* k = nullptr;
+    LogupKernelCache& kc = logup_kernel_cache();
+    { std::lock_guard<std::mutex> lk(kc.mu); auto it = kc.map.find({ctx, key}); if (it != kc.map.end()) k = it->second; }
+    if (!k) {
+        uint32_t n_kernels = 1;
+        const std::string src = generate_air_source(ctx, program, n_instr, n_regs, &n_kernels, nullptr, true);
+        nx_air_kernel* nk = nullptr;
+        NX_TRY(compile_source(ctx, src, n_kernels, n_cols, n_econsts, n_c, &nk, 2));
+        std::lock_guard<std::mutex> lk(kc.mu);
+        kc.map.insert({{ctx, key}, nk});
+        k = nk;
+    }
+    // one device block: the column table and the secure constants, then count[] (u64) and first[] (u32)
+    const size_t b_cols = (size_t)n_cols * 8, b_ec = (size_t)n_econsts * 16, b_cnt = (size_t)n_c * 8, b_first = (size_t)n_c * 4;
+    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_ec = al(b_cols), o_cnt = o_ec + al(b_ec), o_first = o_cnt + al(b_cnt), total = o_first + al(b_first) + 16;
+    std::vector<uint8_t> host(total, 0);
+    if (b_cols) memcpy(host.data(), d_cols, b_cols);
+    if (b_ec) memcpy(host.data() + o_ec, econsts, b_ec);
+    memset(host.data() + o_first, 0xff, b_first);
+    uint8_t* blob = nullptr;
+    NX_TRY(dev_alloc(ctx, total, (void**)&blob));
+    int rc = upload_async_staged(ctx, blob, host.data(), total);
+    if (rc == NX_OK) {
+        const void* p_cols = blob; const void* p_ec = blob + o_ec; void* p_cnt = blob + o_cnt; void* p_first = blob + o_first;
+        int ls = (int)log_size; uint32_t n = 1u << log_size;
+        void* args[] = {&p_cols, &p_ec, &ls, &p_cnt, &p_first, &n};
+        for (hipFunction_t fn : k->fns) {
+            const hipError_t e = hipModuleLaunchKernel(fn, (n + 255) / 256, 1, 1, 256, 1, 1, 0, ctx->stream, args, nullptr);
+            if (e != hipSuccess) { rc = hip_fail(ctx, e, who, __FILE__, __LINE__); break; }
+        }
+    }
+    std::vector<uint64_t> count(n_c); std::vector<uint32_t> first(n_c);
+    if (rc == NX_OK) rc = copy_d2h_blocking(ctx, host.data() + o_cnt, blob + o_cnt, total - o_cnt);
+    dev_free(ctx, blob);
+    NX_TRY(rc);
+    memcpy(count.data(), host.data() + o_cnt, b_cnt); memcpy(first.data(), host.data() + o_first, b_first);
+    const size_t begin = out->size();
+    for (uint32_t j = 0; j < n_c; j++) {
+        if (!count[j]) continue;
+        nx_check_failure f; memset(&f, 0, sizeof f);
+        f.component = component; f.constraint = j; f.first_row = first[j]; f.n_rows = count[j];
+        out->push_back(f);
+    }
+    // value[] at first_row: the mask rows gathered (nx_gather) and the program run on the host, once per distinct row
+    const size_t n_val = std::min(n_values, out->size() - begin);
+    if (n_val == 0) return NX_OK;
+    std::vector<uint32_t> rows;
+    for (size_t q = 0; q < n_val; q++) rows.push_back((*out)[begin + q].first_row);
+    std::sort(rows.begin(), rows.end()); rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+    std::vector<const uint32_t*> gp; std::vector<uint64_t> gi;
+    const uint32_t mask = (1u << log_size) - 1;
+    const uint32_t* some = nullptr;                     // a column only dead code loads may be NULL: any valid word will do, it is never used
+    for (uint32_t c = 0; c < n_cols && !some; c++) some = d_cols[c];
+    for (uint32_t row : rows)
+        for (uint32_t i = 0; i < n_instr; i++) {
+            const nx_cinstr& in = program[i];
+            if (in.op != NX_C_LOAD && in.op != NX_C_LOADE) continue;
+            const uint64_t pos = host_pos_of_coset_row((row + (uint32_t)(int32_t)in.b) & mask, log_size);
+            for (uint32_t w = 0; w < (in.op == NX_C_LOADE ? 4u : 1u); w++) {
+                const uint32_t* col = d_cols[in.a + w];
+                gp.push_back(col ? col : some); gi.push_back(col ? pos : 0);
+            }
+        }
+    std::vector<uint32_t> words(gp.size());
+    if (!gp.empty()) NX_TRY(nx_gather(ctx, gp.data(), gi.data(), gp.size(), words.data()));
+    const size_t per_row = rows.empty() ? 0 : gp.size() / rows.size();
+    std::vector<uint32_t> vals;
+    for (size_t ri = 0; ri < rows.size(); ri++) {
+        host_run_program(program, n_instr, n_regs, econsts, words.data() + ri * per_row, &vals);
+        for (size_t q = 0; q < n_val; q++) {
+            nx_check_failure& f = (*out)[begin + q];
+            if (f.first_row == rows[ri]) memcpy(f.value, &vals[4 * (size_t)f.constraint], 16);
+        }
+    }
+    return NX_OK;
+}
+
+// the report both entry points return: the array, the count, NX_OK / NX_ERR_PROTOCOL with the first failure in words
+int air_check_report(nx_ctx* ctx, const std::vector<nx_check_failure>& all, const std::vector<uint32_t>& comp_log, nx_check_failure* failures, uint32_t cap, uint32_t* n_failed) {
+    const size_t n = std::min<size_t>(cap, all.size());
+    if (n) memcpy(failures, all.data(), n * sizeof(nx_check_failure));
+    *n_failed = (uint32_t)all.size();
+    if (all.empty()) return NX_OK;
+    const nx_check_failure& f = all[0];
+    return set_err(ctx, NX_ERR_PROTOCOL, "component " + std::to_string(f.component) + " constraint " + std::to_string(f.constraint) + ": not zero on " + std::to_string(f.n_rows) + " of " +
+                                             std::to_string((uint64_t)1 << comp_log[f.component]) + " rows, first at row " + std::to_string(f.first_row));
+}
+
+}  // namespace nx
+
+extern "C" {
+
+int nx_air_check_source(const nx_cinstr* program, uint32_t n_instr, uint32_t n_regs, uint32_t n_cols, uint32_t n_econsts, uint32_t n_constraints, char** h_source_out) {
+    if (!program || !h_source_out) return set_err(nullptr, NX_ERR_ARG, "nx_air_check_source: NULL argument");
+    uint32_t n_c = 0;
+    NX_TRY(validate_air_program(nullptr, program, n_instr, n_regs, n_cols, n_econsts, &n_c));
+    if (n_c != n_constraints) return set_err(nullptr, NX_ERR_ARG, "nx_air_check_source: the program adds a different number of constraints than announced");
+    const std::string src = generate_air_source(nullptr, program, n_instr, n_regs, nullptr, nullptr, true);
+    *h_source_out = (char*)malloc(src.size() + 1);
+    if (!*h_source_out) return set_err(nullptr, NX_ERR_OOM, "nx_air_check_source: malloc failed");
+    std::copy(src.c_str(), src.c_str() + src.size() + 1, *h_source_out);
+    return NX_OK;
+}
+
+int nx_air_check(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_instr, uint32_t n_regs, const uint32_t* const* d_cols, uint32_t n_cols, const uint32_t* econsts,
+                 uint32_t n_econsts, uint32_t n_constraints, uint32_t log_size, nx_check_failure* failures, uint32_t cap, uint32_t* n_failed) {
+    NX_GUARD(ctx);
+    if (!n_failed || (cap && !failures)) return set_err(ctx, NX_ERR_ARG, "nx_air_check: NULL argument");
+    std::vector<nx_check_failure> all;
+    NX_TRY(air_check_component(ctx, "nx_air_check", program, n_instr, n_regs, d_cols, n_cols, econsts, n_econsts, n_constraints, log_size, 0, cap, &all));
+    return air_check_report(ctx, all, {log_size}, failures, cap, n_failed);
+}
+
+}  // extern "C"

@@ -304,7 +304,7 @@ struct GenericAir : AirProver {
     std::vector<std::vector<std::vector<int>>> offs;     // tree -> column -> union of sampled offsets (first-appearance order)
     std::vector<std::vector<uint32_t>> tree_logs;
     ~GenericAir() override { for (auto& c : comps) if (c.owned) nx_air_kernel_destroy(c.owned); }
-    int check(const CommitmentSchemeProver& cs);
+    int check(const CommitmentSchemeProver& cs, size_t n_trees = 0);   // n_trees: the first trees of cs are the statement's (0 = all of them)
     int compute_composition(CommitmentSchemeProver& cs, QM31 random_coeff, DevBuf* out_polys, uint32_t* out_log) override;
     void mask_points(QPt oods, MaskPoints* points) override;
     QM31 eval_composition_at_point(QPt point, const SampledValues& sv, QM31 rc) override;

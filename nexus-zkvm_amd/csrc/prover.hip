@@ -1206,9 +1206,9 @@ int prove_core(nx_ctx* ctx, CommitmentSchemeProver& cs, Blake2sChannel& channel,
 // transcript prefix (reference machine.rs:198-263) through the session and nx_prover_prove runs stwo::prover::prove on the device.
 
 // the consistency rules of oracle-side gair_check: every committed column claimed, sizes agree, loads inside the masks
-int GenericAir::check(const CommitmentSchemeProver& cs) {
+int GenericAir::check(const CommitmentSchemeProver& cs, size_t n_trees) {
     if (cs.trees.empty()) return set_err(ctx, NX_ERR_ARG, "nx_prover_prove: at least one trace tree must be committed first");
-    const int NT = (int)cs.trees.size();                 // the reference commits 3 (preprocessed, main, interaction); the count is the session's
+    const int NT = (int)(n_trees ? n_trees : cs.trees.size());                 // the reference commits 3 (preprocessed, main, interaction); the count is the session's
     if (comps.empty()) return set_err(ctx, NX_ERR_ARG, "nx_prover_prove: no components");
     tree_logs.assign(NT, {}); offs.assign(NT, {});
     std::vector<std::vector<char>> claimed(NT);
@@ -2058,12 +2058,10 @@ int nx_prover_tree_commit_host_narrow(nx_prover* p, const void* const* h_cols, c
     return tree_commit_host(p, h_cols, kinds, coset_order, keep_idx, n_keep, d_keep, root, "nx_prover_tree_commit_host_narrow");
 }
 
-int nx_prover_prove(nx_prover* p, const nx_air_component* comps, uint32_t n_comps, uint32_t** proof_words, size_t* n_words, nx_prove_stats* stats) {
-    NX_GUARD(p ? p->ctx : nullptr);
-    if (!p || !comps || !proof_words || !n_words) return set_err(p ? p->ctx : nullptr, NX_ERR_ARG, "nx_prover_prove: NULL argument");
+}  // extern "C" (re-opened below)
+// the component array of nx_prover_prove / nx_prover_check as the session's GenericAir (the refusals are the same texts for both)
+static int components_from_abi(nx_prover* p, const nx_air_component* comps, uint32_t n_comps, nxhip::GenericAir& air) {
     nx_ctx* ctx = p->ctx;
-    if (p->open) return set_err(ctx, NX_ERR_ARG, "nx_prover_prove: a tree is begun but not committed");
-    nxhip::GenericAir air; air.ctx = ctx;
     for (uint32_t i = 0; i < n_comps; i++) {
         const nx_air_component& u = comps[i];
         if (!u.program || (u.n_cols && (!u.col_tree || !u.col_index || !u.mask_count)) || (u.n_econsts && !u.econsts)) return set_err(ctx, NX_ERR_ARG, "nx_prover_prove: NULL pointer in a component");
@@ -2083,6 +2081,17 @@ int nx_prover_prove(nx_prover* p, const nx_air_component* comps, uint32_t n_comp
         }
         air.comps.push_back(std::move(g));
     }
+    return NX_OK;
+}
+extern "C" {
+
+int nx_prover_prove(nx_prover* p, const nx_air_component* comps, uint32_t n_comps, uint32_t** proof_words, size_t* n_words, nx_prove_stats* stats) {
+    NX_GUARD(p ? p->ctx : nullptr);
+    if (!p || !comps || !proof_words || !n_words) return set_err(p ? p->ctx : nullptr, NX_ERR_ARG, "nx_prover_prove: NULL argument");
+    nx_ctx* ctx = p->ctx;
+    if (p->open) return set_err(ctx, NX_ERR_ARG, "nx_prover_prove: a tree is begun but not committed");
+    nxhip::GenericAir air; air.ctx = ctx;
+    NX_TRY(components_from_abi(p, comps, n_comps, air));
     if (p->proved) { while (p->cs->trees.size() > p->pre_trees) p->cs->trees.pop_back(); p->channel = p->pre_channel; }   // a second prove of the session
     ctx->symmetric_failure = false;
     if (p->cs->dist.on()) {
@@ -2120,6 +2129,44 @@ int nx_prover_prove(nx_prover* p, const nx_air_component* comps, uint32_t n_comp
     memcpy(out, w.data(), w.size() * 4);
     *proof_words = out; *n_words = w.size();
     return NX_OK;
+}
+
+// assert_constraints_on_polys for the session's committed statement: every recorded constraint on every row of every component's TRACE
+// domain.  The committed columns hold coefficients, so the columns a component loads are evaluated on its own trace domain into scratch
+// — the forward transform that undoes the commit's interpolation (log_expand 0) —, checked (air_jit.hip) and freed before the next
+// component.  Reads the session, changes nothing of it: no channel call, no tree touched.
+int nx_prover_check(nx_prover* p, const nx_air_component* comps, uint32_t n_comps, nx_check_failure* failures, uint32_t cap, uint32_t* n_failed) {
+    NX_GUARD(p ? p->ctx : nullptr);
+    if (!p || !comps || !n_failed || (cap && !failures)) return set_err(p ? p->ctx : nullptr, NX_ERR_ARG, "nx_prover_check: NULL argument");
+    nx_ctx* ctx = p->ctx;
+    if (p->has_comm) return set_err(ctx, NX_ERR_ARG, "nx_prover_check: one GPU (checking a row-sharded trace is not supported)");
+    if (p->open) return set_err(ctx, NX_ERR_ARG, "nx_prover_check: a tree is begun but not committed");
+    nxhip::GenericAir air; air.ctx = ctx;
+    NX_TRY(components_from_abi(p, comps, n_comps, air));
+    NX_TRY(air.check(*p->cs, p->proved ? p->pre_trees : 0));      // after a prove the composition tree follows the trace trees
+    std::vector<nx_check_failure> all;
+    std::vector<uint32_t> comp_log;
+    for (uint32_t ci = 0; ci < n_comps; ci++) {
+        const nxhip::GComponent& g = air.comps[ci];
+        comp_log.push_back(g.log_size);
+        const uint32_t n_cols = (uint32_t)g.cols.size();
+        std::vector<char> used;
+        air_subset_columns(g.prog.data(), (uint32_t)g.prog.size(), g.n_regs, n_cols, nullptr, &used);
+        std::vector<const uint32_t*> src;
+        for (uint32_t k = 0; k < n_cols; k++) if (used[k]) src.push_back(p->cs->trees[g.cols[k].first].polys[g.cols[k].second].ptr);
+        nxhip::DevBuf scratch;
+        std::vector<const uint32_t*> ptrs(n_cols, nullptr);
+        if (!src.empty()) {
+            NX_TRY(scratch.alloc(ctx, src.size() << g.log_size));
+            auto dst = nxhip::col_ptrs(scratch.p, (uint32_t)src.size(), g.log_size);
+            NX_TRY(nx_evaluate_batch(ctx, p->tw, src.data(), (uint32_t)src.size(), g.log_size, 0, dst.data()));
+            size_t q = 0;
+            for (uint32_t k = 0; k < n_cols; k++) if (used[k]) ptrs[k] = dst[q++];
+        }
+        NX_TRY(air_check_component(ctx, "nx_prover_check", g.prog.data(), (uint32_t)g.prog.size(), g.n_regs, ptrs.data(), n_cols, g.econsts.data(), (uint32_t)g.econsts.size() / 4,
+                                   g.n_constraints, g.log_size, ci, cap > all.size() ? cap - all.size() : 0, &all));
+    }
+    return air_check_report(ctx, all, comp_log, failures, cap, n_failed);
 }
 
 }  // extern "C"

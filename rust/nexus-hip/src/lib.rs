@@ -436,6 +436,19 @@ impl Session {
         unsafe { sys::nx_free_host(words as *mut std::ffi::c_void) };
         Ok(v)
     }
+    /// stwo_constraint_framework::assert_constraints_on_polys for the committed statement (`nx_prover_check`): every recorded constraint on
+    /// every row of every component's trace domain.  `Ok(vec![])` when all hold; otherwise up to `max_failures` entries in (component,
+    /// constraint) order — the failing constraint, its first natural trace row, its value there, the number of failing rows.  Does not
+    /// touch the transcript: call it before or after `prove`, any number of times.  One GPU.
+    pub fn check(&mut self, comps: &[RecordedComponent], max_failures: usize) -> Result<Vec<sys::nx_check_failure>, HipError> {
+        let raw = raw_components(comps);
+        let mut out = vec![sys::nx_check_failure { component: 0, constraint: 0, first_row: 0, value: [0; 4], n_rows: 0 }; max_failures];
+        let mut n_failed = 0u32;
+        match unsafe { sys::nx_prover_check(self.p, raw.as_ptr(), raw.len() as u32, out.as_mut_ptr(), max_failures as u32, &mut n_failed) } {
+            sys::NX_OK | sys::NX_ERR_PROTOCOL => { out.truncate((n_failed as usize).min(max_failures)); Ok(out) }
+            rc => try_check(self.ctx, rc).map(|_| Vec::new()),
+        }
+    }
     pub fn ctx(&self) -> *mut sys::nx_ctx { self.ctx }
     /// Per-context policy (include/nexus_hip.h `nx_ctx_set_option`), e.g. `("air.degree_split", 0)` to evaluate every constraint on the
     /// component's full domain like Stwo does.  No option changes a proof byte.  An unknown name or a value out of range is `Err(Argument)`.
