@@ -570,20 +570,22 @@ def test_empty_and_single_column_inputs(be, oracle):
     be.set_hash_mode(0)
 
 
-def test_boundary_values_stay_canonical(be, oracle):
-    """Columns made of 0, 1, p-1 and p-2 only: every sum/difference/product hits the reduction boundaries; the LDE must be
-    canonical (< p, committed as raw words) and bit-exact."""
-    log = 14
+@pytest.mark.parametrize("log", [5, 13, 14, 16])
+def test_boundary_values_stay_canonical(be, oracle, log):
+    """Columns made of 0, 1, p-1 and p-2 only (one all p-1, one all 0, one alternating 0, p-1): every sum/difference/product hits the
+    reduction boundaries; the LDE must be canonical (< p, committed as raw words) and bit-exact — on every route of the transform: the
+    small kernel (log 5), a single pass (13), the 2^14 route and the fused middle (16)."""
     rng = np.random.default_rng(99)
     vals = rng.choice(np.array([0, 1, P - 1, P - 2], np.uint32), size=(4, 1 << log))
     vals[0, :] = P - 1
     vals[1, :] = 0
+    vals = np.concatenate([vals, np.tile(np.array([0, P - 1], np.uint32), 1 << (log - 1))[None, :]])
     otw = oracle.Twiddles(log + 1)
     cols = be.columns_from_host(vals)
     lde = be.lde(be.precompute_twiddles(log), cols, 1)
     got_c, got_l = cols.to_cpu(), lde.to_cpu()
     assert got_c.max() < P and got_l.max() < P
-    for c in range(4):
+    for c in range(5):
         coeff = otw.interpolate(vals[c])
         assert np.array_equal(got_c[c], coeff)
         assert np.array_equal(got_l[c], otw.evaluate(coeff, log + 1))
