@@ -813,6 +813,42 @@ int nx_logup_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_instr, ui
                      uint32_t n_cols, const uint32_t* econsts, uint32_t n_econsts, uint32_t log_size, uint32_t n_logup_cols,
                      uint32_t* const* d_out, char** h_source_out);
 
+/* The TABLE side of a lookup: how often every table row was used, counted on the device.  The reference verifier refuses a proof
+ * whose claimed sums do not cancel (prover/src/machine.rs:343; prover2/machine/src/verify.rs:145-160); they cancel only when the
+ * table component's main-trace column holds the real counts.  The reference counts on the CPU, into the SideNote: the v1
+ * Multiplicity<LEN, L> extensions (prover/src/extensions/multiplicity.rs:143-237), the bitwise tables, prover2's range_multiplicity /
+ * bitwise_multiplicity components.  Here the looked-up columns are read where they are, in HBM.
+ * uses: every place a tuple is looked up — n_key_cols device columns of 2^log_size canonical M31 words in ANY row order (bit-reversed
+ * trace columns go in as they are) and the numerator column d_weight in the same order (NULL: every row counts 1; padding rows carry
+ * 1 - is_padding).  At most 65536 uses, 2^30 rows per use and 2^32 rows in all per call (NX_ERR_ARG beyond: the sums stay below 2^63).
+ * Key: the key columns are the tuple entries that determine the table row ([value] of a range table, (b, c) of a bitwise table); a
+ * tuple (v_0 .. v_{k-1}) with v_i < 2^key_bits[i] has the key sum_i v_i << (key_bits[0] + .. + key_bits[i-1]).  1 <= n_key_cols <= 4,
+ * 1 <= key_bits[i], sum of key_bits <= 24.  A lookup whose remaining entries disagree with the table is not seen here: its claimed
+ * sums will not cancel.
+ * d_table: n_key_cols device columns of 2^log_table words, the table component's preprocessed key columns as stored, in whatever order
+ * they were committed (the reference's RangeValues holds value i at position i).  A table value outside its key_bits, or two table
+ * rows with one key, is NX_ERR_ARG.
+ * d_mult (device, 2^log_table words — typically the column nx_prover_tree_begin handed out for the table component, so nothing crosses
+ * PCIe): d_mult[pos] = (sum of the weights of all rows of all uses whose key is the key of table row pos) mod p, canonical.  The sums
+ * are exact 64-bit integers reduced once; only integer additions and minima are combined across lanes, so every run gives the same
+ * words.
+ * Missing rows: a row of nonzero weight (or of a use without weights) is missing when an entry is >= 2^key_bits[i] or no table row has
+ * its key; rows of weight 0 never are.  n_missing / first_missing_use / first_missing_pos (each optional): their number and the smallest
+ * (use index, storage position) among them.  With a missing row the call returns NX_ERR_PROTOCOL and nx_last_error names that row and
+ * its values, "use 2 row position 17: (300) is not a row of the table"; d_mult is filled for the rows that are present.
+ * Key spaces of up to 2^NX_MULT_LDS_MAX_KEY_BITS keys are counted in block-private LDS counters, wider ones with global atomics.
+ * Blocking (it reports a count); temporaries (8 bytes per key of the key space) come from the context's allocator and are released
+ * before it returns. */
+#define NX_MULT_LDS_MAX_KEY_BITS 12
+typedef struct nx_lookup_use {
+    const uint32_t* const* d_values;  /* n_key_cols device columns, 2^log_size canonical M31 words each, ANY row order */
+    const uint32_t* d_weight;         /* NULL: every row counts 1; else a canonical M31 numerator column in the same row order */
+    uint32_t log_size;
+} nx_lookup_use;
+int nx_logup_multiplicities(nx_ctx* ctx, const nx_lookup_use* uses, uint32_t n_uses, uint32_t n_key_cols, const uint32_t* key_bits,
+                            const uint32_t* const* d_table, uint32_t log_table, uint32_t* d_mult, uint64_t* n_missing,
+                            uint32_t* first_missing_use, uint64_t* first_missing_pos);
+
 /* Config #2: LDE + Blake2s commit of n_cols random columns of 2^log_size rows (already resident,
  * bit-reversed evaluations, overwritten by their coefficients); d_lde receives the LDE columns. */
 int nx_lde_commit(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, uint32_t n_cols, uint32_t log_size,

@@ -20,6 +20,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "nexus_hip.h")
 
 P = (1 << 31) - 1
 NX_OK = 0
+NX_ERR_PROTOCOL = -4
 HASH_BLAKE2S, HASH_BLAKE2S_RAW0 = 0, 1
 FRI_ALPHA_PREV, FRI_ALPHA_FIRST = 0, 1
 # element kinds of the narrow host-column entry points (NX_COL_* of include/nexus_hip.h)
@@ -609,6 +610,14 @@ class LogupFrac(C.Structure):
     """nx_logup_frac of include/nexus_hip.h."""
     _fields_ = [("d_tuple_cols", C.c_void_p), ("n_tuple_cols", C.c_uint32), ("alpha_powers", C.c_void_p), ("z", C.c_void_p), ("d_mult", C.c_void_p),
                 ("scale", C.c_void_p)]
+
+
+class LookupUse(C.Structure):
+    """nx_lookup_use of include/nexus_hip.h."""
+    _fields_ = [("d_values", C.c_void_p), ("d_weight", C.c_void_p), ("log_size", C.c_uint32)]
+
+
+MULT_LDS_MAX_KEY_BITS = 12   # NX_MULT_LDS_MAX_KEY_BITS: widest key space nx_logup_multiplicities counts in LDS
 
 
 class ProveStats(C.Structure):
@@ -1254,6 +1263,33 @@ class HipBackend:
         cs = np.zeros((n, 4), np.uint32)
         self._chk(self.L.nx_logup_finalize_last_batch(self.ctx, cols4_list[0].log_size if n else 0, ptrs, n, cs.ctypes.data_as(C.c_void_p)))
         return cs
+
+    def logup_multiplicities(self, uses, table_ptrs, log_table, key_bits, out_ptr, want_rc=False):
+        """The table side of a lookup (nx_logup_multiplicities): out_ptr[pos] = how often (weighted, mod p) the key of table row pos
+        occurs in `uses`.  uses: (value_ptrs, weight_ptr or None, log_size) each, value_ptrs = one device pointer per key column in
+        any row order; table_ptrs: the table's key columns (2^log_table words each); key_bits: bits per key column; out_ptr: device
+        pointer of 2^log_table words, e.g. the table component's main column from ProverSession.tree_begin.  Returns (n_missing,
+        first_use, first_pos) of the rows that are in no table row — (0, 0, 0) when the lookup is sound; raises as the neighbours do
+        on every code but NX_ERR_PROTOCOL (rows missing: the counts of the others are still written).  want_rc: also the code."""
+        kb = _u32(key_bits).reshape(-1)
+        k = len(kb)
+        if len(table_ptrs) != k:
+            raise NexusHipError(f"logup_multiplicities: {len(table_ptrs)} table columns for {k} key columns")
+        arr, keep = (LookupUse * max(1, len(uses)))(), []
+        for i, (vals, weight, log_size) in enumerate(uses):
+            if len(vals) != k:
+                raise NexusHipError(f"logup_multiplicities: use {i} has {len(vals)} value columns for {k} key columns")
+            vp = (C.c_void_p * k)(*[int(v) for v in vals])
+            keep.append(vp)
+            arr[i] = LookupUse(C.cast(vp, C.c_void_p), int(weight) if weight is not None else None, int(log_size))
+        tp = (C.c_void_p * k)(*[int(t) for t in table_ptrs])
+        n, fu, fp = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        rc = self.L.nx_logup_multiplicities(self.ctx, arr, len(uses), k, kb.ctypes.data_as(C.c_void_p), tp, int(log_table), C.c_void_p(int(out_ptr)),
+                                            C.byref(n), C.byref(fu), C.byref(fp))
+        if rc not in (NX_OK, NX_ERR_PROTOCOL):
+            self._chk(rc)
+        res = (n.value, fu.value, fp.value)
+        return (res, rc) if want_rc else res
 
     # ---- FriOps ----
     def fold_circle_into_line(self, tw, dst4, src4, alpha):

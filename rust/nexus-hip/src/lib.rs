@@ -421,6 +421,23 @@ impl Session {
         try_check(self.ctx, unsafe { sys::nx_logup_finalize_last(self.ctx, comp.log_size, out[out.len() - 4..].as_ptr(), claimed.as_mut_ptr()) })?;
         Ok(claimed)
     }
+    /// The table component's multiplicity column counted on the device (`nx_logup_multiplicities`): what the reference's `SideNote`
+    /// counts on the CPU for its range-check and bitwise tables (prover/src/extensions/multiplicity.rs:143-237).  `uses`: (key columns,
+    /// numerator column or null, log_size) of every place the relation is looked up, in any row order; `table`: the table's preprocessed
+    /// key columns of 2^log_table words; `mult`: 2^log_table words, typically the table component's main column from `tree_begin`.
+    /// Returns (number of rows that are in no table row, the first of them as (use, position)): (0, None) for a sound lookup; with
+    /// missing rows the counts of the others are still written.
+    pub fn logup_multiplicities(&mut self, uses: &[(&[*const u32], *const u32, u32)], key_bits: &[u32], table: &[*const u32], log_table: u32, mult: *mut u32)
+        -> Result<(u64, Option<(u32, u64)>), HipError> {
+        if table.len() != key_bits.len() || uses.iter().any(|u| u.0.len() != key_bits.len()) { return Err(HipError::Argument("logup_multiplicities: one column per key_bits entry".into())); }
+        let raw: Vec<sys::nx_lookup_use> = uses.iter().map(|u| sys::nx_lookup_use { d_values: u.0.as_ptr(), d_weight: u.1, log_size: u.2 }).collect();
+        let (mut n, mut first_use, mut first_pos) = (0u64, 0u32, 0u64);
+        match unsafe { sys::nx_logup_multiplicities(self.ctx, raw.as_ptr(), raw.len() as u32, key_bits.len() as u32, key_bits.as_ptr(), table.as_ptr(), log_table, mult, &mut n, &mut first_use, &mut first_pos) } {
+            sys::NX_OK => Ok((0, None)),
+            sys::NX_ERR_PROTOCOL => Ok((n, Some((first_use, first_pos)))),
+            rc => try_check(self.ctx, rc).map(|_| (0, None)),
+        }
+    }
     /// Compiled AIR / fraction kernels are kept in `dir` across processes (`nx_air_cache_dir`): the first proof of a process loads
     /// them in milliseconds instead of paying hiprtc (seconds for an AIR of the reference's size).  Process-wide.
     pub fn kernel_cache_dir(dir: &str) -> Result<(), HipError> {
