@@ -81,9 +81,10 @@ int nx_ctx_set_hash_mode(nx_ctx* ctx, int mode);
  * (highest level built by the fused sub-tree launch; 0 = one launch per level), "merkle.top" (the level, 1..10, from which ONE block
  * builds the rest of a tree), "merkle.pair_levels" (two node-only levels per launch
  * above it), "fri.device_channel", "fri.tail" (0 = off, 1 = the FRI layers of <= 2^11 points in one launch,
- * 2..11 = from 2^that many points), "logup.scan_tiled", "logup.per_column", "merkle.fused" (0 = off, else the smallest log size from which a tree of <= 4 columns of one
- * size gets its leaf hash and 6 levels in one launch), "machine.logup_program" (1: nx_prove_machine builds every wide-tuple component's interaction
- * trace through nx_logup_program).  "host.pack_threads" (1..64; default
+ * 2..11 = from 2^that many points), "logup.scan_tiled", "logup.per_column", "merkle.fused" (0..31, default 21; 0 = off, else the smallest log size from which a tree of <= 4 columns of one
+ * size gets its leaf hash and 6 levels in one launch), "machine.logup_program" (default 0; 1: nx_prove_machine builds every wide-tuple component's interaction
+ * trace through nx_logup_program), "trace.vec4" (1, the default: nx_trace_program runs a program whose loads all have offset 0 with four
+ * storage positions per lane — 16-byte loads and stores — instead of one row per lane).  "host.pack_threads" (1..64; default
  * min(16, hardware threads)): host threads that pack NX_COL_U32_AS_U16 / NX_COL_U32_AS_U8 columns of the narrow upload entry points.
  * Unknown names and out-of-range values are NX_ERR_ARG.
  * None of them changes a result: proofs, roots and transforms are bit-identical under every setting. */
@@ -848,6 +849,46 @@ typedef struct nx_lookup_use {
 int nx_logup_multiplicities(nx_ctx* ctx, const nx_lookup_use* uses, uint32_t n_uses, uint32_t n_key_cols, const uint32_t* key_bits,
                             const uint32_t* const* d_table, uint32_t log_table, uint32_t* d_mult, uint64_t* n_missing,
                             uint32_t* first_missing_use, uint64_t* first_missing_pos);
+
+/* ------------------------------------------- derived trace columns filled on the device from a recorded ROW PROGRAM --------------
+ * The reference fills the main trace on the CPU: MachineChip::fill_main_trace (prover/src/traits.rs:34-40) runs every chip on every
+ * row, and almost every chip is a row-local integer function of a few seed columns — AddChip's ValueA bytes and CarryFlag bits from
+ * ValueB / ValueC (prover/src/chips/instructions/i/add.rs:26-96), SllChip's Rem / Qt / shift bits (sll.rs:33-111), the range, bit-op,
+ * compare and branch chips; the preprocessed is_first and counter columns depend on the row number only (prover/src/trace/
+ * preprocessed.rs:65-99).  A host that uploads the seed columns and derives the rest here moves a fraction of the trace over PCIe.
+ * A trace program is an nx_cinstr array over the BASE-FIELD register file: NX_C_LOAD (row offset taken in natural trace order, row
+ * (i + o) mod 2^log_size, the rule of nx_air_check and nx_logup_program), NX_C_CONST, NX_C_ADD, NX_C_SUB, NX_C_MUL, NX_C_NEG and the
+ * opcodes below.  Registers always hold canonical words: the 32-bit integer result r of an integer opcode is written as r mod p (only
+ * OR, XOR and SHL can reach p), so there is no error path at run time. */
+enum {
+    NX_T_STORE = 32,    /* cols[a][row] = B[b]                                   (dst must be 0)                       */
+    NX_T_STORE_IF = 33, /* if (B[dst] != 0) cols[a][row] = B[b]; the column keeps its content elsewhere: several chips  */
+                        /* share one column (ValueA), each on the rows of its own opcode flag                           */
+    NX_T_ROW = 34,      /* B[dst] = the natural trace row i (the VM step), not the storage position                     */
+    NX_T_AND = 35, NX_T_OR = 36, NX_T_XOR = 37, /* B[dst] = B[a] op B[b], the canonical words as 32-bit integers        */
+    NX_T_SHL = 38,      /* B[dst] = (B[a] << B[b]) truncated to 32 bits; a count >= 32 gives 0                          */
+    NX_T_SHR = 39,      /* B[dst] = B[a] >> B[b]; a count >= 32 gives 0                                                 */
+    NX_T_LTU = 40, NX_T_EQ = 41, /* B[dst] = 1 if B[a] < B[b] / B[a] == B[b] as integers, else 0                        */
+    NX_T_INV = 42       /* B[dst] = the M31 inverse of B[a]; the inverse of 0 is 0 (is-zero helper columns)             */
+};
+/* Runs the program once per row and stores into d_cols, TRACE-DOMAIN EVALUATIONS in bit-reversed circle-domain order, 2^log_size
+ * words each (1 <= log_size <= 30) — what nx_prover_tree_begin hands out before the commit; preprocessed, main and scratch columns
+ * may be mixed in one table, entries the program neither loads nor stores may be NULL.  One work-item per storage position (it
+ * derives its natural row once), stores go to the lane's own position; a program whose loads all have offset 0 (the row-local chips)
+ * runs with four consecutive positions per lane and 16-byte loads and stores when every column it touches is 16-byte aligned and the
+ * trace has at least four rows (context option "trace.vec4"; the same words either way).  A program too large for the instruction cache is cut at
+ * store boundaries into kernels of at most "air.segment" estimated instructions, launched one after the other.
+ * Refused with NX_ERR_ARG (nx_last_error names the instruction): a secure-field, constraint or fraction opcode; a program without a
+ * store; a register read before an earlier instruction wrote it; a LOAD, at any offset, of a column that some store of the program
+ * targets (lanes would race: chain two calls instead); a loaded or stored column whose pointer is NULL; an output column whose
+ * pointer equals that of another entry of d_cols; a register out of range, a column index >= n_cols, an immediate >= p.
+ * Stream-ordered like nx_air_eval: validation errors are returned at once, a later commit, check or download orders after the
+ * launch.  Compiled by hiprtc on first use and kept per context, keyed by the program bytes (nx_air_cache_dir and the helper-process
+ * compilation apply; released by nx_ctx_destroy).  No device memory is allocated: the pointer table travels through the context's
+ * staging ring.  h_source_out (optional; when it is the only output wanted ctx and d_cols may be NULL and no GPU is needed): the
+ * generated HIP source (free with nx_free_host). */
+int nx_trace_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_instr, uint32_t n_regs, uint32_t* const* d_cols,
+                     uint32_t n_cols, uint32_t log_size, char** h_source_out);
 
 /* Config #2: LDE + Blake2s commit of n_cols random columns of 2^log_size rows (already resident,
  * bit-reversed evaluations, overwritten by their coefficients); d_lde receives the LDE columns. */

@@ -190,6 +190,20 @@ def logup_program_source(program, n_cols, n_logup_cols):
     return out
 
 
+def trace_program_source(program, n_cols):
+    """The HIP source nx_trace_program generates for a trace program, ProgramBuilder.build_trace_program() (needs no GPU and no context)."""
+    L = load_library()
+    ins = _u32(program.instrs).reshape(-1)
+    src = C.c_void_p()
+    rc = L.nx_trace_program(None, ins.ctypes.data_as(C.c_void_p), len(ins) // 4, program.n_regs, None, n_cols, 4, C.byref(src))
+    if rc != 0:
+        raise NexusHipError(f"nx_trace_program failed ({rc}): {L.nx_last_error(None).decode()}")
+    try:
+        return C.string_at(src.value).decode()
+    finally:
+        L.nx_free_host(src)
+
+
 def air_check_source(program, n_cols):
     """The HIP source of the check kernels nx_air_check compiles for a recorded program (needs no GPU and no context)."""
     L = load_library()
@@ -1244,6 +1258,14 @@ class HipBackend:
         self._chk(self.L.nx_logup_program(self.ctx, ins.ctypes.data_as(C.c_void_p), len(ins) // 4, program.n_regs, ptrs, len(column_ptrs),
                                           ec.ctypes.data_as(C.c_void_p) if len(ec) else None, len(ec) // 4, log_size, n_logup_cols, optr, None))
         return outs
+
+    def trace_program(self, program, cols, log_size):
+        """nx_trace_program: derived trace columns filled on the device.  program = ProgramBuilder.build_trace_program(); cols: one
+        device address (int) per column of the table the program's LOADs and stores index — trace-domain evaluations of 2^log_size
+        words, e.g. what ProverSession.tree_begin handed out (None where the program touches nothing).  Stream-ordered."""
+        ins = _u32(program.instrs).reshape(-1)
+        ptrs = (C.c_void_p * max(1, len(cols)))(*[int(c) if c else None for c in cols])
+        self._chk(self.L.nx_trace_program(self.ctx, ins.ctypes.data_as(C.c_void_p), len(ins) // 4, program.n_regs, ptrs, len(cols), int(log_size), None))
 
     def logup_finalize_last(self, col4, log_size=None):
         """LogupTraceGenerator::finalize_last in place; returns the claimed sum (4 words).  col4: a 4-column DeviceColumns, or (with

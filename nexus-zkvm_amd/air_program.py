@@ -21,11 +21,22 @@ Lookups are recorded the way the reference declares them (prover/src/components/
 and yield BOTH the logup constraints (in `build()`, exactly stwo-constraint-framework's finalize_logup_batched) and the fraction
 program `build_logup()` that nx_logup_program turns into the interaction trace on the device — the same relation entries, so the
 trace satisfies the constraints by construction.
+
+Derived trace columns are recorded the same way (nx_trace_program: the row-local part of the reference's fill_main_trace):
+    b, c = pb.next_trace_mask(0)[0], pb.next_trace_mask(1)[0]
+    s = b + c                                                     # bytes: the integer sum
+    pb.store(2, pb.band(s, 255)); pb.store(3, pb.shr(s, 8))       # ValueA byte and CarryFlag
+    pb.store_if(flag, 4, pb.bxor(b, c))                           # only on the rows of this chip's flag
+    prog = pb.build_trace_program()
 """
 import numpy as np
 
 P = (1 << 31) - 1
 (LOAD, CONST, ADD, SUB, MUL, NEG, CONSTE, ADDE, SUBE, MULE, MULEB, ADDEB, LOADE, CONSTRAINT_B, CONSTRAINT_E, FRAC, FRACB) = range(17)
+# trace programs (nx_trace_program): NX_T_* of include/nexus_hip.h
+(T_STORE, T_STORE_IF, T_ROW, T_AND, T_OR, T_XOR, T_SHL, T_SHR, T_LTU, T_EQ, T_INV) = range(32, 43)
+_BIN = ("add", "sub", "mul", "adde", "sube", "mule", "muleb", "addeb", "band", "bor", "bxor", "shl", "shr", "ltu", "eq")
+_UN = ("neg", "inv")
 
 
 class Expr:
@@ -102,6 +113,7 @@ class ProgramBuilder:
         self.entries = []        # relation entries since the last finalize_logup*: (numerator Expr, denominator Expr)
         self.fractions = []      # finalized: (numerator id, denominator id, logup column)
         self.n_logup_cols = 0
+        self.stores = []         # trace programs: (column, value id, flag id or None) in declaration order
 
     def _node(self, key, kind):
         if key in self.cse:
@@ -165,6 +177,61 @@ class ProgramBuilder:
 
     def add_constraint(self, expr):
         self.constraints.append(expr.id)
+
+    # ---- trace programs (nx_trace_program): integer operations on the canonical words, the natural row, stores
+    def _b(self, x):
+        x = x if isinstance(x, Expr) else self.const(int(x))
+        assert x.kind == "B", "trace programs run over the base field"
+        return x
+
+    def _int2(self, op, x, y, commutative=False):
+        x, y = self._b(x), self._b(y)
+        if commutative and y.id < x.id:
+            x, y = y, x
+        return self._node((op, x.id, y.id), "B")
+
+    def row(self):
+        """The natural trace row i (the VM step), not the storage position."""
+        return self._node(("row",), "B")
+
+    def band(self, x, y):
+        return self._int2("band", x, y, True)
+
+    def bor(self, x, y):
+        return self._int2("bor", x, y, True)
+
+    def bxor(self, x, y):
+        return self._int2("bxor", x, y, True)
+
+    def shl(self, x, n):
+        """x << n truncated to 32 bits, then mod p; a count >= 32 gives 0"""
+        return self._int2("shl", x, n)
+
+    def shr(self, x, n):
+        return self._int2("shr", x, n)
+
+    def ltu(self, x, y):
+        return self._int2("ltu", x, y)
+
+    def eq(self, x, y):
+        return self._int2("eq", x, y, True)
+
+    def inv(self, x):
+        """The M31 inverse; inv(0) = 0"""
+        return self._node(("inv", self._b(x).id), "B")
+
+    def store(self, col, value):
+        """cols[col][row] = value"""
+        self.stores.append((int(col), self._b(value).id, None))
+
+    def store_if(self, flag, col, value):
+        """cols[col][row] = value on the rows where flag != 0; the column keeps its content elsewhere"""
+        self.stores.append((int(col), self._b(value).id, self._b(flag).id))
+
+    def build_trace_program(self):
+        """The program nx_trace_program runs: the recorded stores in declaration order, each preceded by what it needs."""
+        assert self.stores, "a trace program needs a store"
+        return self._lower([("store", st) for st in self.stores])
 
     # ---- lookups (stwo-constraint-framework: RelationEntry, EvalAtRow::add_to_relation, finalize_logup*)
     def relation(self, z, alpha, n):
@@ -237,7 +304,7 @@ class ProgramBuilder:
 
     def _lower(self, roots):
         nodes = self.nodes
-        root_ids = lambda r: [r[1]] if r[0] == "cons" else [r[1][0], r[1][1]]
+        root_ids = lambda r: [r[1]] if r[0] == "cons" else [r[1][0], r[1][1]] if r[0] == "frac" else [r[1][1]] + ([r[1][2]] if r[1][2] is not None else [])
         # liveness: only nodes reachable from a root are emitted
         needed = [False] * len(nodes)
         stack = [i for r in roots for i in root_ids(r)]
@@ -247,19 +314,17 @@ class ProgramBuilder:
                 continue
             needed[i] = True
             key = nodes[i][0]
-            if key[0] in ("add", "sub", "mul", "adde", "sube", "mule", "muleb", "addeb"):
+            if key[0] in _BIN:
                 stack += [key[1], key[2]]
-            elif key[0] == "neg":
+            elif key[0] in _UN:
                 stack.append(key[1])
         # emission order: constraints in declaration order (alpha power j belongs to the j-th add_constraint), each preceded
         # by the not-yet-emitted part of its expression (post-order), so values are computed right before their first use and
         # the register file stays small; the column loads of every group of 8 constraints are hoisted in front of the
         # group so that runs of LOADs form (the kernel issues a run's reads together).
-        BIN = ("add", "sub", "mul", "adde", "sube", "mule", "muleb", "addeb")
-
         def children(i):
             key = nodes[i][0]
-            return [key[1], key[2]] if key[0] in BIN else [key[1]] if key[0] == "neg" else []
+            return [key[1], key[2]] if key[0] in _BIN else [key[1]] if key[0] in _UN else []
 
         order, emitted = [], set()
 
@@ -296,9 +361,11 @@ class ProgramBuilder:
                 last[i] = pos
             elif what == "frac":
                 last[i[0]] = pos; last[i[1]] = pos
+            elif what == "store":
+                for a in root_ids((what, i)):
+                    last[a] = pos
             else:
-                key = nodes[i][0]
-                for a in ([key[1], key[2]] if key[0] in ("add", "sub", "mul", "adde", "sube", "mule", "muleb", "addeb") else [key[1]] if key[0] == "neg" else []):
+                for a in children(i):
                     last[a] = pos
         # linear-scan allocation: B registers and E register quads from separate pools
         free_b, free_e, n_b, n_e = [], [], 0, 0
@@ -323,9 +390,10 @@ class ProgramBuilder:
                 touched = [i]
             elif what == "frac":
                 touched = [i[0], i[1]]
+            elif what == "store":
+                touched = root_ids((what, i))
             else:
-                key = nodes[i][0]
-                touched = [key[1], key[2]] if key[0] in ("add", "sub", "mul", "adde", "sube", "mule", "muleb", "addeb") else [key[1]] if key[0] == "neg" else []
+                touched = children(i)
             for a in set(touched):
                 if last.get(a) == pos and a in slot:
                     kind, idx = slot[a]
@@ -340,7 +408,8 @@ class ProgramBuilder:
             return idx if kind == "B" else n_b + 4 * idx
 
         out = []
-        opmap = {"add": ADD, "sub": SUB, "mul": MUL, "adde": ADDE, "sube": SUBE, "mule": MULE, "muleb": MULEB, "addeb": ADDEB}
+        opmap = {"add": ADD, "sub": SUB, "mul": MUL, "adde": ADDE, "sube": SUBE, "mule": MULE, "muleb": MULEB, "addeb": ADDEB,
+                 "band": T_AND, "bor": T_OR, "bxor": T_XOR, "shl": T_SHL, "shr": T_SHR, "ltu": T_LTU, "eq": T_EQ}
         for what, i in order:
             if what == "cons":
                 out.append((CONSTRAINT_B if nodes[i][1] == "B" else CONSTRAINT_E, 0, reg(i), 0))
@@ -348,6 +417,10 @@ class ProgramBuilder:
             if what == "frac":
                 assert nodes[i[1]][1] == "E", "a relation's denominator is a secure-field value"
                 out.append((FRACB if nodes[i[0]][1] == "B" else FRAC, i[2], reg(i[0]), reg(i[1])))
+                continue
+            if what == "store":
+                col, value, flag = i
+                out.append((T_STORE, 0, col, reg(value)) if flag is None else (T_STORE_IF, reg(flag), col, reg(value)))
                 continue
             key = nodes[i][0]
             if key[0] == "load":
@@ -360,6 +433,10 @@ class ProgramBuilder:
                 out.append((CONSTE, reg(i), key[1], 0))
             elif key[0] == "neg":
                 out.append((NEG, reg(i), reg(key[1]), 0))
+            elif key[0] == "inv":
+                out.append((T_INV, reg(i), reg(key[1]), 0))
+            elif key[0] == "row":
+                out.append((T_ROW, reg(i), 0, 0))
             else:
                 out.append((opmap[key[0]], reg(i), reg(key[1]), reg(key[2])))
         instrs = np.array(out, dtype=np.uint32).reshape(-1, 4)

@@ -140,7 +140,11 @@ static uint32_t instr_cost(uint32_t op) {   // rough gfx950 instruction counts o
     switch (op) {
     case NX_C_LOAD: return 6; case NX_C_CONST: return 1; case NX_C_ADD: case NX_C_SUB: return 4; case NX_C_MUL: return 7; case NX_C_NEG: return 3;
     case NX_C_CONSTE: return 4; case NX_C_ADDE: case NX_C_SUBE: return 16; case NX_C_MULE: return 85; case NX_C_MULEB: return 30; case NX_C_ADDEB: return 4;      // MULE / CONSTRAINT_E: the lazy q_mul of round 6 (160 / 170 before)
-    case NX_C_LOADE: return 24; case NX_C_CONSTRAINT_B: return 14; case NX_C_CONSTRAINT_E: return 100; default: return 1;
+    case NX_C_LOADE: return 24; case NX_C_CONSTRAINT_B: return 14; case NX_C_CONSTRAINT_E: return 100;
+    // trace programs (nx_trace_program): INV is the 37-product exponentiation chain
+    case NX_T_STORE: return 3; case NX_T_STORE_IF: return 5; case NX_T_ROW: return 1; case NX_T_AND: case NX_T_SHR: case NX_T_LTU: case NX_T_EQ: return 2;
+    case NX_T_OR: case NX_T_XOR: return 5; case NX_T_SHL: return 7; case NX_T_INV: return 260;
+    default: return 1;
     }
 }
 // estimated-instruction budget of one generated kernel: ~70 KB of code per kernel at the default 9000; measured sweep 1500..60000
@@ -171,6 +175,11 @@ static void instr_ranges(const nx_cinstr& in, std::vector<RegRange>* reads, RegR
     case NX_C_CONSTRAINT_E: reads->push_back({in.a, 4}); break;
     case NX_C_FRAC: reads->push_back({in.a, 4}); reads->push_back({in.b, 4}); break;
     case NX_C_FRACB: reads->push_back({in.a, 1}); reads->push_back({in.b, 4}); break;
+    case NX_T_STORE: reads->push_back({in.b, 1}); break;
+    case NX_T_STORE_IF: reads->push_back({in.b, 1}); reads->push_back({in.dst, 1}); break;      // dst is the flag: read, not written
+    case NX_T_ROW: *write = {in.dst, 1}; break;
+    case NX_T_AND: case NX_T_OR: case NX_T_XOR: case NX_T_SHL: case NX_T_SHR: case NX_T_LTU: case NX_T_EQ: reads->push_back({in.a, 1}); reads->push_back({in.b, 1}); *write = {in.dst, 1}; break;
+    case NX_T_INV: reads->push_back({in.a, 1}); *write = {in.dst, 1}; break;
     default: break;
     }
 }
@@ -365,6 +374,11 @@ static ProgDeps program_deps(const nx_cinstr* prog, uint32_t n_instr, uint32_t n
         case NX_C_CONSTRAINT_E: use(i, in.a, 4); cons_index[i] = n_c++; break;
         case NX_C_FRAC: use(i, in.a, 4); use(i, in.b, 4); break;
         case NX_C_FRACB: use(i, in.a, 1); use(i, in.b, 4); break;
+        case NX_T_STORE: use(i, in.b, 1); break;
+        case NX_T_STORE_IF: use(i, in.b, 1); use(i, in.dst, 1); break;
+        case NX_T_ROW: def(i, in.dst, 1); break;
+        case NX_T_AND: case NX_T_OR: case NX_T_XOR: case NX_T_SHL: case NX_T_SHR: case NX_T_LTU: case NX_T_EQ: use(i, in.a, 1); use(i, in.b, 1); def(i, in.dst, 1); break;
+        case NX_T_INV: use(i, in.a, 1); def(i, in.dst, 1); break;
         default: break;
         }
     }
@@ -941,7 +955,8 @@ int nx_air_eval(nx_ctx* ctx, const nx_air_kernel* k, const uint32_t* const* d_co
 // order); a row offset is taken in natural coset order, where the trace step is +1.
 namespace nx {
 
-static const char* LOGUP_PRELUDE = R"SRC(
+// a^(p-2): the M31 inverse, 0 for 0 (shared by the logup fraction kernels and NX_T_INV of the trace kernels)
+static const char* M_INV_PRELUDE = R"SRC(
 FI u32 m_sqr(u32 a) { return m_mul(a, a); }
 FI u32 m_sqn(u32 a, int n) { for (int i = 0; i < n; i++) a = m_sqr(a); return a; }
 FI u32 m_inv(u32 a) {
@@ -949,7 +964,8 @@ FI u32 m_inv(u32 a) {
     const u32 t24 = m_mul(m_sqn(t16, 8), t8), t28 = m_mul(m_sqn(t24, 4), t4), t29 = m_mul(m_sqr(t28), a);
     return m_mul(m_sqn(t29, 2), a);
 }
-// the norm part of a QM31 inverse: x^-1 = (a, -b) D^-1, D = a^2 - (2 + i) b^2 in CM31, D^-1 = conj(D) / (D.a^2 + D.b^2)
+)SRC";
+static const char* LOGUP_PRELUDE = R"SRC(// the norm part of a QM31 inverse: x^-1 = (a, -b) D^-1, D = a^2 - (2 + i) b^2 in CM31, D^-1 = conj(D) / (D.a^2 + D.b^2)
 )SRC"
 #ifndef NX_Q_MUL_NAIVE
 R"SRC(// D = x.a^2 - (2 + i) x.b^2 and x^-1 = (x.a, -x.b) conj(D) / |D|^2: every coordinate one lazy sum of at most four products (field.cuh q_norm_cm / q_conj_times)
@@ -1108,7 +1124,7 @@ int validate_logup_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_ins
 
 static std::string generate_logup_source(const nx_ctx* ctx, const nx_cinstr* prog, uint32_t n_instr, uint32_t n_regs, uint32_t* n_kernels) {
     const ProgDeps pd = program_deps(prog, n_instr, n_regs);
-    std::string s = std::string(AIR_PRELUDE) + TRACE_ROWS_PRELUDE + LOGUP_PRELUDE;
+    std::string s = std::string(AIR_PRELUDE) + TRACE_ROWS_PRELUDE + M_INV_PRELUDE + LOGUP_PRELUDE;
     std::vector<char> batch_end(n_instr, 0);
     { int last = -1; for (uint32_t i = 0; i < n_instr; i++) if (prog[i].op == NX_C_FRAC || prog[i].op == NX_C_FRACB) { if (last >= 0 && prog[last].dst != prog[i].dst) batch_end[last] = 1; last = (int)i; } if (last >= 0) batch_end[last] = 1; }
     uint32_t n_seg = 0, cost = 0, first_col = 0;
@@ -1394,3 +1410,229 @@ int nx_air_check(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_instr, uint32
 }
 
 }  // extern "C"
+
+// ================================================================ trace programs (nx_trace_program) =========================
+// The fourth emission mode of this file: the straight-line body of a recorded program with STORES as its roots — derived trace columns
+// (row-local integer functions of a few seed columns, what the reference's fill_main_trace computes on the CPU) filled where the
+// trace lives.  One lane per storage position of the trace domain; the lane's natural row is derived once; every load of a kernel is
+// issued before its arithmetic (a loaded column is never a stored one, so nothing orders them), every store goes to the lane's own
+// position.  Large programs are cut at store boundaries (backward slices, as the constraint kernels); a loaded column is never a
+// stored one, so the kernels are independent apart from the order of the stores into one column, which the launch order keeps.
+namespace nx {
+
+static const char* TRACE_PRELUDE = R"SRC(
+#define GW(p) ((__attribute__((address_space(1))) u32*)(p))
+typedef u32 v4u __attribute__((ext_vector_type(4)));
+#define G4(p) ((__attribute__((address_space(1))) const v4u*)(p))
+#define GW4(p) ((__attribute__((address_space(1))) v4u*)(p))
+// the 32-bit integer result r of an integer opcode as a canonical word: r mod p (r < 2^32 = 2 p + 2, so 2^31 hi + lo = hi + lo <= p + 1)
+FI u32 t_red(u32 r) { return m_csub((r & P) + (r >> 31)); }
+FI u32 t_shl(u32 a, u32 n) { return n < 32 ? t_red(a << (n & 31)) : 0u; }
+FI u32 t_shr(u32 a, u32 n) { return n < 32 ? a >> (n & 31) : 0u; }
+)SRC";
+
+static bool is_trace_store(uint32_t op) { return op == NX_T_STORE || op == NX_T_STORE_IF; }
+static bool trace_vec4_wanted(const nx_ctx* ctx) {      // per context ("trace.vec4"); source-only generation without a context (CPU suite): the process default
+    if (ctx) return ctx->opt.trace_vec4 != 0;
+    const char* e = getenv("NX_TRACE_VEC4");
+    return !(e && *e == '0');
+}
+
+int validate_trace_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_instr, uint32_t n_regs, uint32_t n_cols) {
+    if (!program) return set_err(ctx, NX_ERR_ARG, "trace program: NULL program");
+    if (n_regs == 0 || n_regs > 4096) return set_err(ctx, NX_ERR_ARG, "trace program: register count out of range");
+    std::vector<char> written(n_regs, 0), stored(n_cols, 0);
+    bool any_store = false;
+    auto bad = [&](uint32_t i, const char* why) { return set_err(ctx, NX_ERR_ARG, std::string("trace program: instruction ") + std::to_string(i) + ": " + why); };
+    std::vector<RegRange> reads; RegRange wr;
+    for (uint32_t i = 0; i < n_instr; i++) {
+        const nx_cinstr& in = program[i];
+        switch (in.op) {
+        case NX_C_LOAD: if (in.a >= n_cols) return bad(i, "column index beyond the column table"); break;
+        case NX_C_CONST: if (in.a >= P) return bad(i, "immediate not below p"); break;
+        case NX_C_ADD: case NX_C_SUB: case NX_C_MUL: case NX_C_NEG: case NX_T_ROW: case NX_T_AND: case NX_T_OR: case NX_T_XOR: case NX_T_SHL: case NX_T_SHR: case NX_T_LTU: case NX_T_EQ:
+        case NX_T_INV: break;
+        case NX_T_STORE: if (in.dst != 0) return bad(i, "dst of a STORE must be 0");
+            [[fallthrough]];
+        case NX_T_STORE_IF: if (in.a >= n_cols) return bad(i, "column index beyond the column table"); stored[in.a] = 1; any_store = true; break;
+        case NX_C_CONSTE: case NX_C_ADDE: case NX_C_SUBE: case NX_C_MULE: case NX_C_MULEB: case NX_C_ADDEB: case NX_C_LOADE: return bad(i, "a secure-field opcode (a trace program runs over the base field)");
+        case NX_C_CONSTRAINT_B: case NX_C_CONSTRAINT_E: return bad(i, "a constraint opcode (the stores are the roots of this program)");
+        case NX_C_FRAC: case NX_C_FRACB: return bad(i, "a fraction opcode (the stores are the roots of this program)");
+        default: return bad(i, "unknown opcode");
+        }
+        instr_ranges(in, &reads, &wr);
+        for (const RegRange& r : reads) {
+            if (r.reg >= n_regs) return bad(i, "register out of range");
+            if (!written[r.reg]) return bad(i, "reads a register no earlier instruction wrote");
+        }
+        if (wr.w) { if (wr.reg >= n_regs) return bad(i, "register out of range"); written[wr.reg] = 1; }
+    }
+    if (!any_store) return set_err(ctx, NX_ERR_ARG, "trace program: no STORE / STORE_IF instruction (nothing would be written)");
+    for (uint32_t i = 0; i < n_instr; i++)
+        if (program[i].op == NX_C_LOAD && stored[program[i].a])
+            return bad(i, "loads a column that a store of this program targets (lanes would race: derive it in a second call)");
+    return NX_OK;
+}
+
+// vec4: FOUR consecutive storage positions per lane, every column read and written as one 16-byte word per lane — the form for
+// programs whose loads all have offset 0 (the row-local chips): the body is emitted once per position over the same register names.
+static std::string generate_trace_kernel(const nx_cinstr* prog, const std::vector<uint32_t>& keep, uint32_t n_regs, const std::string& name, bool vec4) {
+    std::string s = "extern \"C\" __attribute__((global)) __attribute__((amdgpu_flat_work_group_size(256, 256))) void " + name + "(u32* const* __restrict__ cols, int log_size, u32 n) {\n";
+    // rows beyond the trace in the last wave are masked
+    if (vec4) s += "  const u32 q = __builtin_amdgcn_workgroup_id_x() * 256 + __builtin_amdgcn_workitem_id_x();\n  if (q >= n / 4) return;\n  const u32 r = 4 * q;\n";
+    else s += "  const u32 r = __builtin_amdgcn_workgroup_id_x() * 256 + __builtin_amdgcn_workitem_id_x();\n  if (r >= n) return;\n";
+    std::vector<int> offs; bool row = false;
+    std::vector<std::pair<uint32_t, int>> loads;       // distinct (column, offset) of this kernel, in program order
+    std::vector<uint32_t> outs; std::set<uint32_t> conditional;        // vec4: the stored columns, those of them with a STORE_IF
+    for (uint32_t i : keep) {
+        if (prog[i].op == NX_T_ROW) row = true;
+        if (is_trace_store(prog[i].op)) {
+            if (std::find(outs.begin(), outs.end(), prog[i].a) == outs.end()) outs.push_back(prog[i].a);
+            if (prog[i].op == NX_T_STORE_IF) conditional.insert(prog[i].a);
+        }
+        if (prog[i].op != NX_C_LOAD) continue;
+        const int o = (int)prog[i].b;
+        if (std::find(offs.begin(), offs.end(), o) == offs.end()) offs.push_back(o);
+        if (std::find(loads.begin(), loads.end(), std::make_pair(prog[i].a, o)) == loads.end()) loads.push_back({prog[i].a, o});
+    }
+    auto off_name = [](int o) { return std::string("row_") + (o < 0 ? "m" : "p") + std::to_string(o < 0 ? -o : o); };
+    auto ld_name = [](uint32_t c, int o) { return "l" + std::to_string(c) + (o < 0 ? "m" : "p") + std::to_string(o < 0 ? -o : o); };
+    if (vec4) {
+        for (const auto& l : loads) s += "  const v4u " + ld_name(l.first, 0) + " = G4(cols[" + std::to_string(l.first) + "])[q];\n";
+        // a column some store writes under a flag keeps its content where the flag is 0: the lane starts from the stored words
+        for (uint32_t c : outs) s += "  v4u o" + std::to_string(c) + (conditional.count(c) ? " = G4(cols[" + std::to_string(c) + "])[q];\n" : " = {0, 0, 0, 0};\n");
+    } else {
+        if (row) s += "  const u32 nat = coset_row_of_pos(r, log_size);\n";
+        for (int o : offs) s += "  const u32 " + off_name(o) + " = trace_row_offset(r, log_size, " + std::to_string(o) + ");\n";
+        for (const auto& l : loads) s += "  const u32 " + ld_name(l.first, l.second) + " = G(cols[" + std::to_string(l.first) + "])[" + off_name(l.second) + "];\n";
+    }
+    auto R = [](uint32_t i) { return "r" + std::to_string(i); };
+    auto fn2 = [&](const nx_cinstr& in, const char* f) { return "  " + R(in.dst) + " = " + f + "(" + R(in.a) + ", " + R(in.b) + ");\n"; };
+    for (int j = 0; j < (vec4 ? 4 : 1); j++) {
+        const std::string J = "[" + std::to_string(j) + "]";
+        if (vec4) { s += "  {\n"; if (row) s += "  const u32 nat = coset_row_of_pos(r + " + std::to_string(j) + ", log_size);\n"; }
+        for (uint32_t k = 0; k < n_regs; k++) s += (k % 16 == 0 ? std::string("  u32 ") : std::string(", ")) + "r" + std::to_string(k) + ((k % 16 == 15 || k + 1 == n_regs) ? " = 0;\n" : " = 0");
+        for (uint32_t i : keep) {
+            const nx_cinstr& in = prog[i];
+            switch (in.op) {
+            case NX_C_LOAD: s += "  " + R(in.dst) + " = " + ld_name(in.a, (int)in.b) + (vec4 ? J : std::string()) + ";\n"; break;
+            case NX_C_CONST: s += "  " + R(in.dst) + " = " + std::to_string(in.a) + "u;\n"; break;
+            case NX_C_ADD: s += fn2(in, "m_add"); break;
+            case NX_C_SUB: s += fn2(in, "m_sub"); break;
+            case NX_C_MUL: s += fn2(in, "m_mul"); break;
+            case NX_C_NEG: s += "  " + R(in.dst) + " = m_neg(" + R(in.a) + ");\n"; break;
+            case NX_T_ROW: s += "  " + R(in.dst) + " = nat;\n"; break;
+            case NX_T_AND: s += "  " + R(in.dst) + " = " + R(in.a) + " & " + R(in.b) + ";\n"; break;
+            case NX_T_OR: s += "  " + R(in.dst) + " = t_red(" + R(in.a) + " | " + R(in.b) + ");\n"; break;
+            case NX_T_XOR: s += "  " + R(in.dst) + " = t_red(" + R(in.a) + " ^ " + R(in.b) + ");\n"; break;
+            case NX_T_SHL: s += fn2(in, "t_shl"); break;
+            case NX_T_SHR: s += fn2(in, "t_shr"); break;
+            case NX_T_LTU: s += "  " + R(in.dst) + " = " + R(in.a) + " < " + R(in.b) + " ? 1u : 0u;\n"; break;
+            case NX_T_EQ: s += "  " + R(in.dst) + " = " + R(in.a) + " == " + R(in.b) + " ? 1u : 0u;\n"; break;
+            case NX_T_INV: s += "  " + R(in.dst) + " = m_inv(" + R(in.a) + ");\n"; break;
+            case NX_T_STORE: s += (vec4 ? "  o" + std::to_string(in.a) + J : "  GW(cols[" + std::to_string(in.a) + "])[r]") + " = " + R(in.b) + ";\n"; break;
+            case NX_T_STORE_IF: s += "  if (" + R(in.dst) + ") " + (vec4 ? "o" + std::to_string(in.a) + J : "GW(cols[" + std::to_string(in.a) + "])[r]") + " = " + R(in.b) + ";\n"; break;
+            default: break;
+            }
+        }
+        if (vec4) s += "  }\n";
+    }
+    if (vec4) for (uint32_t c : outs) s += "  GW4(cols[" + std::to_string(c) + "])[q] = o" + std::to_string(c) + ";\n";
+    return s + "}\n";
+}
+
+static std::string generate_trace_source(const nx_ctx* ctx, const nx_cinstr* prog, uint32_t n_instr, uint32_t n_regs, uint32_t* n_kernels, bool vec4) {
+    const ProgDeps pd = program_deps(prog, n_instr, n_regs);
+    std::string s = std::string(AIR_PRELUDE) + TRACE_ROWS_PRELUDE + M_INV_PRELUDE + TRACE_PRELUDE;
+    uint32_t n_seg = 0, cost = 0;
+    std::vector<char> in_seg(n_instr, 0);
+    auto add_slice = [&](uint32_t root) {
+        uint32_t added = 0;
+        std::vector<uint32_t> st{root};
+        while (!st.empty()) {
+            uint32_t i = st.back(); st.pop_back();
+            if (in_seg[i]) continue;
+            in_seg[i] = 1; added += instr_cost(prog[i].op);
+            for (uint32_t d : pd.deps[i]) if (!in_seg[d]) st.push_back(d);
+        }
+        return added;
+    };
+    auto flush = [&]() {
+        std::vector<uint32_t> keep;
+        for (uint32_t i = 0; i < n_instr; i++) if (in_seg[i]) keep.push_back(i);
+        s += generate_trace_kernel(prog, keep, n_regs, n_seg == 0 ? std::string("air_kernel") : "air_kernel_" + std::to_string(n_seg), vec4);
+        n_seg++;
+        std::fill(in_seg.begin(), in_seg.end(), 0); cost = 0;
+    };
+    const uint32_t budget = segment_budget(ctx) / (vec4 ? 4 : 1);          // the body is emitted four times
+    bool any = false;
+    for (uint32_t i = 0; i < n_instr; i++) {
+        if (!is_trace_store(prog[i].op)) continue;
+        if (any && cost >= budget) { flush(); any = false; }
+        cost += add_slice(i); any = true;
+    }
+    if (any) flush();
+    *n_kernels = n_seg;
+    return s;
+}
+
+}  // namespace nx
+
+extern "C" int nx_trace_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_instr, uint32_t n_regs, uint32_t* const* d_cols, uint32_t n_cols, uint32_t log_size,
+                                char** h_source_out) {
+    NX_GUARD(ctx);
+    if (!program) return set_err(ctx, NX_ERR_ARG, "nx_trace_program: NULL argument");
+    if (log_size < 1 || log_size > 30) return set_err(ctx, NX_ERR_ARG, "nx_trace_program: log_size out of range");
+    NX_TRY(validate_trace_program(ctx, program, n_instr, n_regs, n_cols));
+    if (d_cols)           // every column the program touches must be there, and an output column must be nobody else's memory
+        for (uint32_t i = 0; i < n_instr; i++) {
+            const nx_cinstr& in = program[i];
+            if (in.op != NX_C_LOAD && !is_trace_store(in.op)) continue;
+            if (!d_cols[in.a]) return set_err(ctx, NX_ERR_ARG, "nx_trace_program: instruction " + std::to_string(i) + ": column " + std::to_string(in.a) + " was passed as NULL");
+            if (is_trace_store(in.op))
+                for (uint32_t c = 0; c < n_cols; c++)
+                    if (c != in.a && d_cols[c] == d_cols[in.a])
+                        return set_err(ctx, NX_ERR_ARG, "nx_trace_program: instruction " + std::to_string(i) + ": output column " + std::to_string(in.a) + " has the pointer of column " + std::to_string(c));
+        }
+    // four positions per lane when every load is row-local, the trace has at least four rows and every touched column is 16-byte aligned
+    bool vec4 = log_size >= 2 && trace_vec4_wanted(ctx);
+    for (uint32_t i = 0; i < n_instr && vec4; i++) {
+        const nx_cinstr& in = program[i];
+        if (in.op == NX_C_LOAD && in.b != 0) vec4 = false;
+        if (d_cols && (in.op == NX_C_LOAD || is_trace_store(in.op)) && ((uintptr_t)d_cols[in.a] & 15)) vec4 = false;
+    }
+    // the kernels: per context, keyed by the program bytes (the cache of the logup and check kernels, another key)
+    std::string key = vec4 ? "trace4|" : "trace|";
+    key.append((const char*)program, (size_t)n_instr * sizeof(nx_cinstr));
+    key += "|" + std::to_string(n_regs) + "|" + std::to_string(n_cols) + "|" + std::to_string(segment_budget(ctx));
+    const nx_air_kernel* k = nullptr;
+    LogupKernelCache& kc = logup_kernel_cache();
+    if (ctx) { std::lock_guard<std::mutex> lk(kc.mu); auto it = kc.map.find({ctx, key}); if (it != kc.map.end()) k = it->second; }
+    uint32_t n_kernels = 1;
+    std::string src;
+    if (!k || h_source_out) src = generate_trace_source(ctx, program, n_instr, n_regs, &n_kernels, vec4);
+    if (h_source_out) {
+        *h_source_out = (char*)malloc(src.size() + 1);
+        if (!*h_source_out) return set_err(ctx, NX_ERR_OOM, "nx_trace_program: malloc failed");
+        std::copy(src.c_str(), src.c_str() + src.size() + 1, *h_source_out);
+    }
+    if (!ctx || !d_cols) { if (h_source_out) return NX_OK; return set_err(ctx, NX_ERR_ARG, "nx_trace_program: a context and the column table are needed to run"); }
+    if (!k) {
+        nx_air_kernel* nk = nullptr;
+        NX_TRY(compile_source(ctx, src, n_kernels, n_cols, 0, 0, &nk, 3));      // outside the lock: entries are per context
+        std::lock_guard<std::mutex> lk(kc.mu);
+        kc.map.insert({{ctx, key}, nk});
+        k = nk;
+    }
+    void* staged = nullptr;
+    NX_TRY(stage(ctx, d_cols, (size_t)n_cols * sizeof(uint32_t*), &staged));
+    const void* p_cols = staged;
+    int ls = (int)log_size; uint32_t n = 1u << log_size;
+    const uint32_t lanes = vec4 ? n / 4 : n;
+    void* args[] = {&p_cols, &ls, &n};
+    for (hipFunction_t fn : k->fns) {       // the segments store their own columns, one launch after the other
+        const hipError_t e = hipModuleLaunchKernel(fn, (lanes + 255) / 256, 1, 1, 256, 1, 1, 0, ctx->stream, args, nullptr);
+        if (e != hipSuccess) return hip_fail(ctx, e, "nx_trace_program", __FILE__, __LINE__);
+    }
+    return NX_OK;
+}

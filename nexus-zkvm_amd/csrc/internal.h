@@ -36,6 +36,7 @@ struct nx_options {
     int machine_logup_program;    // "machine.logup_program": nx_prove_machine builds the interaction trace of every wide-tuple component (NX_LOGUP_TUPLES != 0) from its recorded relation entries (nx_logup_program) instead of nx_logup_cols (same bytes; components with expression numerators always do)
     int machine_reuse_pre;        // "machine.reuse_preprocessed": nx_prove_machine keeps the committed preprocessed tree of a statement shape in the context and adopts it in later proofs (nx_prover_tree_adopt's rule; default 0: every proof commits it afresh, as the reference does)
     int air_degree_split;         // "air.degree_split": constraints of degree <= 3 of a component with a bound > 1 are evaluated on the log_size + 1 domain
+    int trace_vec4;               // "trace.vec4": nx_trace_program runs a program whose loads are all row-local with four storage positions per lane (16-byte loads and stores) instead of one row per lane
     int host_pack_threads;        // "host.pack_threads": host threads that pack NX_COL_U32_AS_* columns (HostFeed)
 };
 

@@ -22,6 +22,7 @@ use std::marker::PhantomData;
 use std::sync::{Mutex, MutexGuard, OnceLock};
 
 pub mod record;
+pub mod trace_program;
 #[cfg(stwo_traits)]
 pub mod backend;
 #[cfg(stwo_traits)]
