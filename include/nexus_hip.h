@@ -850,6 +850,62 @@ int nx_logup_multiplicities(nx_ctx* ctx, const nx_lookup_use* uses, uint32_t n_u
                             const uint32_t* const* d_table, uint32_t log_table, uint32_t* d_mult, uint64_t* n_missing,
                             uint32_t* first_missing_use, uint64_t* first_missing_pos);
 
+/* ------------------------------------------- memory-checking columns: what the PREVIOUS access to the same address left behind ----
+ * The reference fills these in one sequential pass over a map: Reg{1,2,3}TsPrev / ValPrev from RegisterMemCheckSideNote::access
+ * (prover/src/chips/memory_check/register_mem_check.rs:53-118,401-425; prover/src/trace/regs.rs:29-37), Ram{1..4}TsPrev / ValPrev from
+ * ReadWriteMemCheckSideNote::last_access (prover/src/chips/instructions/i/load_store.rs:180-221; prover/src/trace/sidenote/mod.rs:
+ * 25-47), ProgCtrPrev from last_access_counter (prover/src/chips/memory_check/program_mem_check.rs:49-96), and from what the map holds
+ * at the end the rows of the final-state tables (FinalPrgMemoryCtr, extensions/final_reg.rs, extensions/ram_init_final.rs).  They are
+ * not row-local, so nx_trace_program refuses them.  Here every access of every stream becomes one element (packed key, handle),
+ * enumerated in time order; a stable LSD radix sort by the key (8-bit digits) then puts every access next to its predecessor, the
+ * first access of a key at the head of its run and the last one at its tail.
+ * TIME ORDER (total): lexicographic in (epoch, natural trace row, index of the stream in `streams`).  The natural row of a stream with
+ * linear == 0 is the coset-order row of the storage position (columns in bit-reversed circle-domain order, the rule of nx_air_check,
+ * nx_logup_program and nx_trace_program); with linear != 0 it is the position itself (a memory image).  Registers: three streams of
+ * one epoch in slot order.  RAM: the initial image as a linear stream of epoch 0 with d_prev == NULL, the four byte streams of the
+ * load/store chip with epoch 1.  Streams may have different log_size (1..30; 0..30 when linear; fewer than 2^31 rows in all, at most
+ * 65536 streams).
+ * KEY: as in nx_logup_multiplicities, entry i < 2^key_bits[i], the packed key is sum_i entry_i << (key_bits[0] + .. + key_bits[i-1]);
+ * 1 <= n_key_cols <= 4, 1 <= key_bits[i], sum of key_bits <= 32.
+ * For a row that accesses (d_flag == NULL or its word != 0): d_prev[c][pos] = payload column c of the latest earlier access with the
+ * same key, from whichever stream (0 where that stream's d_payload[c] is NULL), or init[c] when there is none; d_ordinal[pos] = the
+ * number of earlier accesses to the key.  For a row that does not access: every d_prev column and d_ordinal get 0 at its position —
+ * the outputs are fully defined, no memset is needed.  1 <= n_payload <= 16; init: n_payload canonical words, NULL = all 0.
+ * summary (optional): one entry per distinct key in ascending order of the packed key — the key, the number of accesses to it and the
+ * payload of its LAST access; the first min(cap, number of keys) entries are written (entries of d_last may be NULL).  *n_keys
+ * (optional) always receives the number of distinct keys; more keys than cap is not an error.
+ * Exact and order-free: only integers are compared, counted and copied, every word is the same on every run.
+ * NX_ERR_ARG (nx_last_error names the argument; nothing is launched): a NULL ctx, streams, key_bits or key column; n_streams of 0 or
+ * above 65536; n_payload of 0 or above 16; bad key_bits; an init word >= p; a log_size outside its range; 2^31 rows or more in all;
+ * an output pointer (d_prev entry, d_ordinal, summary array) equal to any other column pointer of the call.  A stream that asks for no
+ * output is fine.  NX_ERR_PROTOCOL: an accessing row holds a key entry >= 2^key_bits[i]; nx_last_error names the smallest (stream,
+ * storage position) and the value ("stream 2 row position 17: key entry 0 holds 300, outside its 8 bits"); the outputs are then
+ * unspecified, the context stays usable.
+ * DEVICE MEMORY: with A = the rows of all streams (every row is an element of the sort, accessing or not) and S = n_streams,
+ *     peak above the caller's columns  <=  18 A + 1024 S + 65536 bytes
+ * (two (key, handle) buffers of 8 A each, the per-block digit counts, A at most and never above 1 MiB, A / 128 for the run heads) and NOTHING per
+ * distinct key: the summary goes straight into the caller's arrays.  Taken from the context's allocator, released before the call
+ * returns.  Blocking.  ceil(sum of key_bits / 8) sort passes, one more when some stream has a d_flag and the sum is a multiple of 8
+ * (rows that do not access sort behind the largest key). */
+typedef struct nx_access_stream {
+    const uint32_t* const* d_key;      /* n_key_cols columns, 2^log_size canonical words                      */
+    const uint32_t* d_flag;            /* NULL: every row is an access; else the row accesses iff word != 0   */
+    const uint32_t* const* d_payload;  /* n_payload columns: what this access leaves behind (current          */
+                                       /* timestamp limbs, current value limbs ...); an entry may be NULL = 0 */
+    uint32_t* const* d_prev;           /* NULL, or n_payload output columns (an entry may be NULL: not wanted) */
+    uint32_t* d_ordinal;               /* NULL, or output: number of earlier accesses to the same key         */
+    uint32_t log_size, epoch, linear;  /* linear != 0: position == row; else bit-reversed circle-domain order */
+} nx_access_stream;
+typedef struct nx_access_summary {     /* optional: one entry per distinct key, ascending packed key           */
+    uint32_t cap;                      /* capacity of the arrays below                                         */
+    uint32_t* d_key;                   /* packed key                                                           */
+    uint32_t* d_count;                 /* accesses to it (FinalPrgMemoryCtr)                                   */
+    uint32_t* const* d_last;           /* n_payload columns: payload of its LAST access (final ts / value)     */
+} nx_access_summary;
+int nx_trace_prev_access(nx_ctx* ctx, const nx_access_stream* streams, uint32_t n_streams, uint32_t n_key_cols,
+                         const uint32_t* key_bits, uint32_t n_payload, const uint32_t* init, const nx_access_summary* summary,
+                         uint64_t* n_keys);
+
 /* ------------------------------------------- derived trace columns filled on the device from a recorded ROW PROGRAM --------------
  * The reference fills the main trace on the CPU: MachineChip::fill_main_trace (prover/src/traits.rs:34-40) runs every chip on every
  * row, and almost every chip is a row-local integer function of a few seed columns — AddChip's ValueA bytes and CarryFlag bits from

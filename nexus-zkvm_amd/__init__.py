@@ -631,6 +631,17 @@ class LookupUse(C.Structure):
     _fields_ = [("d_values", C.c_void_p), ("d_weight", C.c_void_p), ("log_size", C.c_uint32)]
 
 
+class AccessStream(C.Structure):
+    """nx_access_stream of include/nexus_hip.h."""
+    _fields_ = [("d_key", C.c_void_p), ("d_flag", C.c_void_p), ("d_payload", C.c_void_p), ("d_prev", C.c_void_p), ("d_ordinal", C.c_void_p),
+                ("log_size", C.c_uint32), ("epoch", C.c_uint32), ("linear", C.c_uint32)]
+
+
+class AccessSummary(C.Structure):
+    """nx_access_summary of include/nexus_hip.h."""
+    _fields_ = [("cap", C.c_uint32), ("d_key", C.c_void_p), ("d_count", C.c_void_p), ("d_last", C.c_void_p)]
+
+
 MULT_LDS_MAX_KEY_BITS = 12   # NX_MULT_LDS_MAX_KEY_BITS: widest key space nx_logup_multiplicities counts in LDS
 
 
@@ -1312,6 +1323,49 @@ class HipBackend:
             self._chk(rc)
         res = (n.value, fu.value, fp.value)
         return (res, rc) if want_rc else res
+
+    def trace_prev_access(self, streams, key_bits, n_payload, init=None, summary=None, want_rc=False):
+        """The memory-checking columns (nx_trace_prev_access): for every access, what the previous access to the same key left behind.
+        streams: dicts in time order within a row — key: one device pointer per key column; log_size; optional flag (pointer, None:
+        every row accesses), payload (n_payload pointers, None entries read as 0), prev (n_payload output pointers or None entries;
+        absent: no output), ordinal (output pointer), epoch (default 0), linear (default False: bit-reversed circle-domain order).
+        key_bits: bits per key column; init: n_payload words an untouched key reads (default 0); summary: (cap, key_ptr, count_ptr,
+        last_ptrs) — one entry per distinct key in ascending order, the first min(cap, n_keys) written.  Returns the number of distinct
+        keys; raises as the neighbours do, also on NX_ERR_PROTOCOL (an accessing row with a key entry outside its bits) unless
+        want_rc: then (n_keys or None, code)."""
+        kb = _u32(key_bits).reshape(-1)
+        k, n_payload = len(kb), int(n_payload)
+
+        def table(ptrs, n, what, i):
+            if ptrs is None:
+                return None
+            if len(ptrs) != n:
+                raise NexusHipError(f"trace_prev_access: stream {i} has {len(ptrs)} {what} columns, {n} expected")
+            t = (C.c_void_p * max(1, n))(*[int(x) if x else None for x in ptrs])
+            keep.append(t)
+            return C.cast(t, C.c_void_p)
+
+        arr, keep = (AccessStream * max(1, len(streams)))(), []
+        for i, s in enumerate(streams):
+            arr[i] = AccessStream(table(s["key"], k, "key", i), int(s["flag"]) if s.get("flag") else None, table(s.get("payload"), n_payload, "payload", i),
+                                  table(s.get("prev"), n_payload, "prev", i), int(s["ordinal"]) if s.get("ordinal") else None, int(s["log_size"]),
+                                  int(s.get("epoch", 0)), int(bool(s.get("linear", False))))
+        iv = None
+        if init is not None:
+            iv = _u32(init).reshape(-1)
+            if len(iv) != n_payload:
+                raise NexusHipError(f"trace_prev_access: {len(iv)} init words for {n_payload} payload columns")
+        sm = None
+        if summary is not None:
+            cap, key_ptr, count_ptr, last_ptrs = summary
+            sm = AccessSummary(int(cap), int(key_ptr) if key_ptr else None, int(count_ptr) if count_ptr else None, table(last_ptrs, n_payload, "summary last", "-"))
+        n = C.c_uint64(0)
+        rc = self.L.nx_trace_prev_access(self.ctx, arr, len(streams), k, kb.ctypes.data_as(C.c_void_p), n_payload, iv.ctypes.data_as(C.c_void_p) if iv is not None else None,
+                                         C.byref(sm) if sm is not None else None, C.byref(n))
+        if want_rc and rc in (NX_OK, NX_ERR_PROTOCOL):
+            return (n.value if rc == NX_OK else None), rc
+        self._chk(rc)
+        return n.value
 
     # ---- FriOps ----
     def fold_circle_into_line(self, tw, dst4, src4, alpha):

@@ -100,10 +100,11 @@ FI u32 row_offset(u32 r, int log_size, int e, int offset) {
 // The TRACE domain (the 2^log_size rows the caller filled, CanonicCoset(log_size).circle_domain() in bit-reversed order): the trace step is
 // +1 in natural coset order and crosses between the two halves of the circle domain, so row_offset above (which needs e > log_size)
 // does not apply.  Shared by the logup fraction kernels and the check kernels.
-static const char* TRACE_ROWS_PRELUDE = R"SRC(
-// natural coset row <-> position in bit-reversed circle-domain order (reference prover/src/trace/utils_external.rs:24-39)
-FI u32 pos_of_coset_row(u32 c, int log) { const u32 N = 1u << log; const u32 d = (c & 1) ? N - 1 - (c >> 1) : (c >> 1); return bitrev(d, log); }
-FI u32 coset_row_of_pos(u32 p, int log) { const u32 N = 1u << log, d = bitrev(p, log); return d < N / 2 ? 2 * d : 2 * (N - 1 - d) + 1; }
+// pos_of_coset_row / coset_row_of_pos: the text of trace_rows.h, which the kernels compiled ahead of time include as code
+#define NX_TRACE_ROWS_AS_TEXT
+static const char* TRACE_ROWS_PRELUDE = "\n"
+#include "trace_rows.h"
+R"SRC(
 FI u32 trace_row_offset(u32 r, int log, int off) { if (off == 0) return r; return pos_of_coset_row((coset_row_of_pos(r, log) + (u32)off) & ((1u << log) - 1), log); }
 )SRC";
 

@@ -187,12 +187,8 @@ __global__ __launch_bounds__(256) void logup_cols_kernel(const LogupBatchFrac* _
     }
 }
 
-// position (bit-reversed circle-domain order) of natural coset row c
-__device__ __forceinline__ u32 pos_of_coset_row(u32 c, int log) {
-    const u32 N = 1u << log;
-    const u32 d = (c & 1) ? N - 1 - (c >> 1) : (c >> 1);
-    return bitrev(d, log);
-}
+// position (bit-reversed circle-domain order) of natural coset row c: pos_of_coset_row
+#include "trace_rows.h"
 
 constexpr int SCAN_ITEMS = 16, SCAN_THREADS = 256, SCAN_BLOCK = SCAN_ITEMS * SCAN_THREADS;
 

@@ -439,6 +439,25 @@ impl Session {
             rc => try_check(self.ctx, rc).map(|_| (0, None)),
         }
     }
+    /// The memory-checking columns filled on the device (`nx_trace_prev_access`): what the reference reads off
+    /// `RegisterMemCheckSideNote::access` (prover/src/trace/regs.rs:29-37), `ReadWriteMemCheckSideNote::last_access`
+    /// (prover/src/trace/sidenote/mod.rs:25-47) and `last_access_counter` (program_mem_check.rs:49-96) in one sequential pass.  `streams`
+    /// in the order the accesses of one row happen (registers: the three slots; RAM: the image as a linear stream of epoch 0, then the
+    /// four byte streams of epoch 1); every `d_key` has one column per `key_bits` entry, every non-null `d_payload` / `d_prev` and
+    /// `summary.d_last` has `n_payload` entries.  `init`: what an untouched key reads (empty: zeros).  Returns the number of distinct
+    /// keys; the first `min(cap, keys)` summary entries (ascending key, access count, payload of the last access: the final-state
+    /// tables) are written.  An accessing row with a key entry outside its bits is `HipError` from NX_ERR_PROTOCOL, naming the row.
+    ///
+    /// # Safety
+    /// Every pointer inside `streams` and `summary` must be valid for the sizes the header states; outputs must not alias.
+    pub unsafe fn trace_prev_access(&mut self, streams: &[sys::nx_access_stream], key_bits: &[u32], n_payload: u32, init: &[u32], summary: Option<&sys::nx_access_summary>)
+        -> Result<u64, HipError> {
+        if !init.is_empty() && init.len() != n_payload as usize { return Err(HipError::Argument("trace_prev_access: one init word per payload column".into())); }
+        let mut n = 0u64;
+        try_check(self.ctx, sys::nx_trace_prev_access(self.ctx, streams.as_ptr(), streams.len() as u32, key_bits.len() as u32, key_bits.as_ptr(), n_payload,
+                                                      if init.is_empty() { std::ptr::null() } else { init.as_ptr() }, summary.map_or(std::ptr::null(), |s| s as *const _), &mut n))?;
+        Ok(n)
+    }
     /// Compiled AIR / fraction kernels are kept in `dir` across processes (`nx_air_cache_dir`): the first proof of a process loads
     /// them in milliseconds instead of paying hiprtc (seconds for an AIR of the reference's size).  Process-wide.
     pub fn kernel_cache_dir(dir: &str) -> Result<(), HipError> {
