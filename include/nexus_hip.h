@@ -946,6 +946,38 @@ enum {
 int nx_trace_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_instr, uint32_t n_regs, uint32_t* const* d_cols,
                      uint32_t n_cols, uint32_t log_size, char** h_source_out);
 
+/* ------------------------------------------- the keccak round trace filled on the device from the instances' input states --------
+ * The reference's KeccakRound component (prover/src/extensions/keccak/round/trace.rs:240-366) is its widest trace: 1705 main columns,
+ * every intermediate 64-bit lane of one keccak-f[1600] round as 8 byte columns.  Row i of an instance holds the state after i rounds,
+ * so the 200 seed columns are not row-local and nx_trace_program cannot fill them; the device needs the 200 bytes of an instance, not
+ * 6.8 KB per row.
+ * d_states: n_instances x 25 little-endian 64-bit lanes in device memory, lane (x, y) at index x + 5 y (KeccakSideNote::inputs); may be
+ * NULL when n_instances == 0.  With rounds = 2^log_rounds, natural trace row r = instance * rounds + i holds the round with constant
+ * RC[first_round + i] applied to the instance's state after i earlier rounds of the component.  Rows r >= n_instances * rounds are
+ * padding: their input state is zero and every derived column follows from it (the iota output is the round-constant bytes, the rest
+ * 0); is_padding is 1 on them.
+ * d_main: NX_KECCAK_ROUND_MAIN_COLS device columns of 2^log_size words, TRACE-DOMAIN EVALUATIONS in bit-reversed circle-domain order
+ * (what nx_prover_tree_begin hands out; the rule of nx_trace_program), in the order the reference's builder allocates them, every lane
+ * as 8 byte columns, low byte first: the 25 input lanes; theta: the 4 chained xors of each of the 5 columns; for each x low / high /
+ * out of rot(C[x+1], 1), then D[x]; the 25 A ^ D lanes, x outer and y inner; rho-pi: low / high / out of each of the 24 nonzero
+ * rotations in (x, y) loop order; chi: not-and, then xor, per (x, y); iota: A[0] ^ RC; is_padding.  A rotation by r has
+ * low = (byte << (r % 8)) & 255, high = byte >> (8 - r % 8) and out byte i = low[(i - r/8) & 7] + high[(i - r/8 + 7) & 7]; rotations
+ * by 8 and 56 still have their three lanes (high = 0).
+ * d_pre: NULL, or NX_KECCAK_ROUND_PRE_COLS columns: the 8 bytes of RC[first_round + (r mod rounds)] on EVERY row, padding included,
+ * then is_last: 1 at natural row 2^log_size - 1, else 0.
+ * d_states_out: NULL, or n_instances x 25 lanes: the state after the component's last round (the reference's `rem`), the next
+ * component's d_states.
+ * Exact integers: the same words on every run.  One work-item per storage position.  Stream-ordered like nx_trace_program; no device
+ * memory is allocated, the pointer table travels through the context's staging ring.
+ * NX_ERR_ARG (nx_last_error names the argument; nothing is launched): first_round + 2^log_rounds > 24; log_size outside 1..30;
+ * n_instances * rounds > 2^log_size; a NULL or repeated column pointer, a pointer shared between d_main and d_pre; d_states NULL with
+ * n_instances > 0; d_states or d_states_out not 8-byte aligned; d_states_out overlapping d_states (lanes of one instance would race);
+ * a NULL ctx. */
+#define NX_KECCAK_ROUND_MAIN_COLS 1705   /* 213 byte-limb lanes of 8 columns + is_padding */
+#define NX_KECCAK_ROUND_PRE_COLS  9      /* 8 round-constant byte columns + is_last */
+int nx_trace_keccak_round(nx_ctx* ctx, const uint64_t* d_states, uint32_t n_instances, uint32_t first_round, uint32_t log_rounds,
+                          uint32_t log_size, uint32_t* const* d_main, uint32_t* const* d_pre, uint64_t* d_states_out);
+
 /* Config #2: LDE + Blake2s commit of n_cols random columns of 2^log_size rows (already resident,
  * bit-reversed evaluations, overwritten by their coefficients); d_lde receives the LDE columns. */
 int nx_lde_commit(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, uint32_t n_cols, uint32_t log_size,

@@ -643,6 +643,7 @@ class AccessSummary(C.Structure):
 
 
 MULT_LDS_MAX_KEY_BITS = 12   # NX_MULT_LDS_MAX_KEY_BITS: widest key space nx_logup_multiplicities counts in LDS
+KECCAK_ROUND_MAIN_COLS, KECCAK_ROUND_PRE_COLS = 1705, 9   # NX_KECCAK_ROUND_MAIN_COLS, NX_KECCAK_ROUND_PRE_COLS
 
 
 class ProveStats(C.Structure):
@@ -1366,6 +1367,21 @@ class HipBackend:
             return (n.value if rc == NX_OK else None), rc
         self._chk(rc)
         return n.value
+
+    def trace_keccak_round(self, states_ptr, n_instances, first_round, log_rounds, log_size, main_ptrs, pre_ptrs=None, states_out_ptr=None):
+        """nx_trace_keccak_round: the KeccakRound component's trace filled on the device.  states_ptr: device address of n_instances x 25
+        64-bit lanes (index x + 5 y; None when n_instances is 0); natural row instance * 2^log_rounds + i holds round first_round + i.
+        main_ptrs: KECCAK_ROUND_MAIN_COLS device addresses of 2^log_size words, e.g. what ProverSession.tree_begin handed out; pre_ptrs:
+        None or KECCAK_ROUND_PRE_COLS addresses (round-constant bytes, is_last); states_out_ptr: None or n_instances x 25 lanes, the
+        state after the component's last round.  Stream-ordered."""
+        if len(main_ptrs) != KECCAK_ROUND_MAIN_COLS:
+            raise NexusHipError(f"trace_keccak_round: {len(main_ptrs)} main columns, {KECCAK_ROUND_MAIN_COLS} expected")
+        if pre_ptrs is not None and len(pre_ptrs) != KECCAK_ROUND_PRE_COLS:
+            raise NexusHipError(f"trace_keccak_round: {len(pre_ptrs)} preprocessed columns, {KECCAK_ROUND_PRE_COLS} expected")
+        mp = (C.c_void_p * KECCAK_ROUND_MAIN_COLS)(*[int(x) if x else None for x in main_ptrs])
+        pp = (C.c_void_p * KECCAK_ROUND_PRE_COLS)(*[int(x) if x else None for x in pre_ptrs]) if pre_ptrs is not None else None
+        self._chk(self.L.nx_trace_keccak_round(self.ctx, C.c_void_p(int(states_ptr)) if states_ptr else None, C.c_uint32(int(n_instances)), C.c_uint32(int(first_round)),
+                                               C.c_uint32(int(log_rounds)), C.c_uint32(int(log_size)), mp, pp, C.c_void_p(int(states_out_ptr)) if states_out_ptr else None))
 
     # ---- FriOps ----
     def fold_circle_into_line(self, tw, dst4, src4, alpha):

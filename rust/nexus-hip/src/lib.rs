@@ -458,6 +458,22 @@ impl Session {
                                                       if init.is_empty() { std::ptr::null() } else { init.as_ptr() }, summary.map_or(std::ptr::null(), |s| s as *const _), &mut n))?;
         Ok(n)
     }
+    /// The KeccakRound component's trace filled on the device (`nx_trace_keccak_round`): what the reference's
+    /// `generate_round_component_trace` builds on the CPU from `convert_input_to_simd`'s rows (prover/src/extensions/keccak/round/
+    /// trace.rs:240-366).  `d_states`: `n_instances` x 25 lanes in device memory (null when there are none); natural row
+    /// `instance * 2^log_rounds + i` holds round `first_round + i`.  `main`: the `NX_KECCAK_ROUND_MAIN_COLS` columns in the builder's
+    /// order, `pre`: empty or the `NX_KECCAK_ROUND_PRE_COLS` round-constant and is_last columns, `d_states_out`: null or where the
+    /// states after the component's last round go (the reference's `rem`, the next component's input).  Stream-ordered.
+    ///
+    /// # Safety
+    /// Every pointer must be valid device memory of the size the header states; columns must not alias.
+    pub unsafe fn trace_keccak_round(&mut self, d_states: *const u64, n_instances: u32, first_round: u32, log_rounds: u32, log_size: u32, main: &[*mut u32], pre: &[*mut u32],
+                                     d_states_out: *mut u64) -> Result<(), HipError> {
+        if main.len() != sys::NX_KECCAK_ROUND_MAIN_COLS as usize { return Err(HipError::Argument("trace_keccak_round: 1705 main columns".into())); }
+        if !pre.is_empty() && pre.len() != sys::NX_KECCAK_ROUND_PRE_COLS as usize { return Err(HipError::Argument("trace_keccak_round: no or 9 preprocessed columns".into())); }
+        try_check(self.ctx, sys::nx_trace_keccak_round(self.ctx, d_states, n_instances, first_round, log_rounds, log_size, main.as_ptr(),
+                                                       if pre.is_empty() { std::ptr::null() } else { pre.as_ptr() }, d_states_out))
+    }
     /// Compiled AIR / fraction kernels are kept in `dir` across processes (`nx_air_cache_dir`): the first proof of a process loads
     /// them in milliseconds instead of paying hiprtc (seconds for an AIR of the reference's size).  Process-wide.
     pub fn kernel_cache_dir(dir: &str) -> Result<(), HipError> {
