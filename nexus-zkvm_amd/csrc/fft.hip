@@ -26,25 +26,46 @@
 namespace nx {
 
 // ------------------------------------------------------------------ twiddles (K2) -----------
-// pt_from_index as a sum of table entries (field.cuh GenTable: no doubling chain per element)
-__global__ void twiddle_kernel(u32* tw, u32* itw, int h, GenTable gen) {
-    u32 p = blockIdx.x * blockDim.x + threadIdx.x;
-    u32 total = 1u << h;
+// All four tables (twiddle, inverse, and both doubled: what m_mul_dbl butterflies consume) in ONE pass, four consecutive words per lane.
+// Word p of a tree of 2^h words, q = 2^h - p: the pad word for q == 1, else entry k = 2^(m+1) - q of the layer of 2^m twiddles
+// (m = floor(log2(q - 1))), the x coordinate of the point with index init + step * bitrev(k, m).  An aligned group of four words with
+// q >= 5 lies in one layer of m >= 2, and bitrev(4 j + r, m) = bitrev(4 j, m) + bitrev(r, 2) 2^(m-2) with step 2^(m-2) = 2^28 in every
+// layer: the four points are ONE sum of table entries (pt_from_index_tbl) moved by 0, 2, 1 and 3 times the order-8 point G^(2^28) — and
+// their inverses one field inversion and nine products (Montgomery's trick; no x is zero: the indices are odd multiples of at most
+// 2^26) instead of four inversions.  The last group of a tree (q = 4 .. 1, layers of 2 and 1 twiddles and the pad) goes word by word.
+__device__ __forceinline__ u32 twiddle_word(const GenTable& gen, int h, u32 q) {
+    if (q == 1) return 1;                   // padding element
+    const int m = 31 - __clz(q - 1);        // this layer holds 2^m twiddles
+    const int l = h - 1 - m;                // doubling depth
+    const u32 k = (2u << m) - q;            // index within the layer
+    const u32 init = (1u << (31 - h - 2)) << l, step = (1u << (31 - h)) << l;
+    return pt_from_index_tbl(gen, (init + step * bitrev(k, m)) & 0x7fffffffu).x;
+}
+__global__ __launch_bounds__(256) void twiddle_kernel(u32* __restrict__ tw, u32* __restrict__ itw, u32* __restrict__ tw2, u32* __restrict__ itw2, int h, GenTable gen) {
+    const u32 total = 1u << h, p = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
     if (p >= total) return;
-    u32 q = total - p;
-    u32 val;
-    if (q == 1) {
-        val = 1;  // padding element
-    } else {
-        int m = 31 - __clz(q - 1);          // this layer holds 2^m twiddles
-        int l = h - 1 - m;                  // doubling depth
-        u32 k = (2u << m) - q;              // index within the layer
-        u32 init = (1u << (31 - h - 2)) << l, step = (1u << (31 - h)) << l;
-        u32 idx = (init + step * bitrev(k, m)) & 0x7fffffffu;
-        val = pt_from_index_tbl(gen, idx).x;
+    const u32 q0 = total - p;               // q of the group's first word
+    if (q0 < 8) {                           // the tree's last group (h == 1: its only two words)
+        for (u32 r = 0; r < 4 && r < q0; r++) {
+            const u32 v = twiddle_word(gen, h, q0 - r), iv = m_inv(v);
+            tw[p + r] = v; itw[p + r] = iv; tw2[p + r] = v << 1; itw2[p + r] = iv << 1;
+        }
+        return;
     }
-    tw[p] = val;
-    itw[p] = m_inv(val);
+    const int m = 31 - __clz(q0 - 1), l = h - 1 - m;
+    const u32 k0 = (2u << m) - q0;
+    const u32 init = (1u << (31 - h - 2)) << l, step = (1u << (31 - h)) << l;
+    const Pt b = pt_from_index_tbl(gen, (init + step * bitrev(k0, m)) & 0x7fffffffu);
+    Pt e1, e2; e1.x = gen.x[28]; e1.y = gen.y[28]; e2.x = gen.x[29]; e2.y = gen.y[29];
+    const Pt e3 = pt_add(e1, e2);
+    const u32 x0 = b.x, x1 = pt_add(b, e2).x, x2 = pt_add(b, e1).x, x3 = pt_add(b, e3).x;      // words r = 0 .. 3: + bitrev(r, 2) 2^28
+    const u32 x01 = m_mul(x0, x1), x23 = m_mul(x2, x3), t = m_inv(m_mul(x01, x23));
+    const u32 i01 = m_mul(t, x23), i23 = m_mul(t, x01);
+    const u32 i0 = m_mul(i01, x1), i1 = m_mul(i01, x0), i2 = m_mul(i23, x3), i3 = m_mul(i23, x2);
+    gst4(tw + p, make_uint4(x0, x1, x2, x3));
+    gst4(itw + p, make_uint4(i0, i1, i2, i3));
+    gst4(tw2 + p, make_uint4(x0 << 1, x1 << 1, x2 << 1, x3 << 1));
+    gst4(itw2 + p, make_uint4(i0 << 1, i1 << 1, i2 << 1, i3 << 1));
 }
 
 // ------------------------------------------------------------------ FFT passes (K3/K4) ------
@@ -405,7 +426,14 @@ int fft_evaluate(nx_ctx* ctx, const nx_twiddles* tw, ColSet polys, uint32_t n_co
 
 // iFFT + LDE per column batch (coefficients stay cache-resident between the two transforms).
 int fft_lde(nx_ctx* ctx, const nx_twiddles* tw, ColSet cols, uint32_t n_cols, uint32_t log_size, uint32_t log_expand, ColSet out) {
+    return fft_lde_from(ctx, tw, cols, cols, n_cols, log_size, log_expand, out);
+}
+// the fused path's first inverse pass takes distinct source and destination columns; the other paths transform in place
+bool fft_lde_reads_source(const nx_ctx* ctx, uint32_t log_size, uint32_t log_expand) { return log_expand == 1 && log_size >= 14 && ctx->opt.fft_fused; }
+int fft_lde_from(nx_ctx* ctx, const nx_twiddles* tw, ColSet src, ColSet cols, uint32_t n_cols, uint32_t log_size, uint32_t log_expand, ColSet out) {
     int n = (int)(log_size + log_expand);
+    const bool in_place = src.base == cols.base && src.stride == cols.stride && src.table == cols.table;
+    if (!in_place && !fft_lde_reads_source(ctx, log_size, log_expand)) return set_err(ctx, NX_ERR_ARG, "fft_lde_from: this size is transformed in place");
     NX_TRY(check_tw(ctx, tw, n));
     tune_init();
     // algorithmic bytes: read N evals, write N coeffs, write M = 2^n LDE words
@@ -417,8 +445,8 @@ int fft_lde(nx_ctx* ctx, const nx_twiddles* tw, ColSet cols, uint32_t n_cols, ui
     for (u32 c0 = 0, bi = 0; c0 < n_cols && rc == NX_OK; c0 += bc, bi++) {
         u32 nb = std::min<u32>(bc, n_cols - c0);
         streams_pick(ctx, (int)bi, ns);
-        if (log_expand == 1 && log_size >= 14 && ctx->opt.fft_fused) {
-            rc = fft13_lde(ctx, tw, sub_colset(cols, c0), nb, (int)log_size, sub_colset(out, c0));   // middle passes fused (fft13.hip)
+        if (fft_lde_reads_source(ctx, log_size, log_expand)) {
+            rc = fft13_lde(ctx, tw, sub_colset(src, c0), sub_colset(cols, c0), nb, (int)log_size, sub_colset(out, c0));   // middle passes fused (fft13.hip)
             continue;
         }
         rc = interpolate_cols(ctx, tw, sub_colset(cols, c0), nb, (int)log_size);
@@ -470,11 +498,6 @@ __global__ void __launch_bounds__(256) widen_kernel(const uint8_t* __restrict__ 
     }
 }
 
-__global__ void twiddle_double_kernel(const u32* tw, const u32* itw, u32* tw2, u32* itw2, u32 n) {
-    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { tw2[i] = tw[i] << 1; itw2[i] = itw[i] << 1; }
-}
-
 }  // namespace nx
 
 using namespace nx;
@@ -496,8 +519,7 @@ int nx_twiddles_create(nx_ctx* ctx, uint32_t log_half_coset, nx_twiddles** out) 
     hipError_t e;
     u32 total = 1u << log_half_coset;
     const GenTable gen = gen_table();
-    hipLaunchKernelGGL(twiddle_kernel, dim3((total + 255) / 256), dim3(256), 0, ctx->stream, t->d_tw, t->d_itw, (int)log_half_coset, gen);
-    hipLaunchKernelGGL(twiddle_double_kernel, dim3((total + 255) / 256), dim3(256), 0, ctx->stream, t->d_tw, t->d_itw, t->d_tw2, t->d_itw2, total);
+    hipLaunchKernelGGL(twiddle_kernel, dim3(((total + 3) / 4 + 255) / 256), dim3(256), 0, ctx->stream, t->d_tw, t->d_itw, t->d_tw2, t->d_itw2, (int)log_half_coset, gen);
     e = hipGetLastError();
     if (e != hipSuccess) { dev_free(ctx, t->d_tw); dev_free(ctx, t->d_itw); dev_free(ctx, t->d_tw2); dev_free(ctx, t->d_itw2); delete t; return hip_fail(ctx, e, "twiddle_kernel", __FILE__, __LINE__); }
     *out = t;

@@ -656,14 +656,16 @@ static int launch_mid(nx_ctx* ctx, const PassMid& m) {
     }
 }
 
-// iFFT in place (coefficients stay in `cols`) + FFT onto 2^(n+1) points in `out`, n >= 14: every pass as in fft13_interpolate /
+// iFFT (coefficients end up in `cols`) + FFT onto 2^(n+1) points in `out`, n >= 14: every pass as in fft13_interpolate /
 // fft13_evaluate except the inverse transform's last pass and the forward transform's first pass, which are one launch.
-int fft13_lde(nx_ctx* ctx, const nx_twiddles* tw, ColSet cols, u32 n_cols, int n, ColSet out) {
+// The evaluations are read from `src` (the inverse transform's first pass reads src and writes cols): src == cols is the in-place
+// transform; a column whose src is another buffer keeps its evaluations there, untouched.
+int fft13_lde(nx_ctx* ctx, const nx_twiddles* tw, ColSet src, ColSet cols, u32 n_cols, int n, ColSet out) {
     std::vector<Plan13> plan = plan13(n, ctx->opt.fft_kmax);
     const size_t P = plan.size();
     if (P < 2) return set_err(ctx, NX_ERR_ARG, "fft13_lde: needs at least two passes");
     for (size_t i = 0; i + 1 < P; i++) {
-        Pass13 a; a.src = cols; a.dst = cols; a.tw = tw->d_itw2; a.tw_log = tw->log_half; a.n = n; a.log_in = n;
+        Pass13 a; a.src = i == 0 ? src : cols; a.dst = cols; a.tw = tw->d_itw2; a.tw_log = tw->log_half; a.n = n; a.log_in = n;
         a.lo = plan[i].lo; a.K = plan[i].K; a.B = plan[i].B; a.scale = 0;
         a.n_cols = n_cols; a.n_groups = 0; a.tiles = 1u << (n - T13_S); a.rep_log = 0;
         NX_TRY(launch13(ctx, true, i == 0, a));

@@ -304,6 +304,10 @@ int tree_pipe_absorb(nx_ctx* ctx, TreePipe* tp, const uint32_t* const* d_cols, u
 int tree_pipe_finish(nx_ctx* ctx, TreePipe* tp, const uint32_t* const* d_small_cols, const uint32_t* small_logs, uint32_t n_small, nx_tree** out);
 int leaf_chain_launch(nx_ctx* ctx, ColSet cs, uint32_t n_cols, uint32_t col_offset, uint32_t total_cols, const uint32_t* state_in, uint32_t* state_out, uint64_t row_begin, uint64_t n_rows);
 int fft_lde(nx_ctx* ctx, const nx_twiddles* tw, ColSet cols, uint32_t n_cols, uint32_t log_size, uint32_t log_expand, ColSet out);
+// fft_lde whose evaluations are read from `src` (coefficients to `cols`, extension to `out`; a column with src != cols keeps its
+// evaluations): only where fft_lde_reads_source says the transform takes a separate source — elsewhere it is in place
+bool fft_lde_reads_source(const nx_ctx* ctx, uint32_t log_size, uint32_t log_expand);
+int fft_lde_from(nx_ctx* ctx, const nx_twiddles* tw, ColSet src, ColSet cols, uint32_t n_cols, uint32_t log_size, uint32_t log_expand, ColSet out);
 
 // fork/join of the side streams around a loop over independent column batches
 int streams_fork(nx_ctx* ctx, int n_streams);
@@ -313,7 +317,7 @@ int streams_join(nx_ctx* ctx, int n_streams);
 // fast path for transforms of >= 2^13 points (fft13.hip)
 int fft13_interpolate(nx_ctx* ctx, const nx_twiddles* tw, ColSet cols, uint32_t n_cols, int n);
 int fft13_evaluate(nx_ctx* ctx, const nx_twiddles* tw, ColSet polys, uint32_t n_cols, int log_in, int n, ColSet out);
-int fft13_lde(nx_ctx* ctx, const nx_twiddles* tw, ColSet cols, uint32_t n_cols, int n, ColSet out);   // blow-up 2, n >= 14: middle passes fused
+int fft13_lde(nx_ctx* ctx, const nx_twiddles* tw, ColSet src, ColSet cols, uint32_t n_cols, int n, ColSet out);   // blow-up 2, n >= 14: middle passes fused
 
 
 }  // namespace nx

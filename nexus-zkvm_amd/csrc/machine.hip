@@ -634,8 +634,9 @@ static int prove_machine(nx_ctx* ctx, const nx_component_spec* comps, uint32_t n
     // A trace tree is consumed by its commitment (the columns become coefficients), and the interaction trace needs evaluations
     // afterwards: the reference clones the whole finalized trace (machine.rs:232) and keeps the preprocessed one; here only the columns
     // the logup fractions read are kept — main columns, and the preprocessed columns of a table component (NX_LOGUP_TABLE).  One GPU:
-    // clones of the filled columns (nx_copy).  Row-sharded: the logup is row-wise, so every GPU needs ITS ROWS of those columns — for
-    // this synthetic trace the generator fills that block directly.  Host hand-over: cloned as the columns arrive (keep list).
+    // nothing is cloned — a kept column is filled (or, handed over by the host, uploaded) into its kept buffer and the commit's inverse
+    // transform reads it from there (keep list).  Row-sharded: the logup is row-wise, so every GPU needs ITS ROWS of those columns — for
+    // this synthetic trace the generator fills that block directly.
     std::vector<DevBuf> kept[2]; kept[0].resize(n_comps); kept[1].resize(n_comps);
     std::vector<ColMap> kept_ptr[2]; kept_ptr[0].resize(n_comps); kept_ptr[1].resize(n_comps);
     auto stage_tree = [&](uint32_t tree, TreeBuilder& tb) -> int {              // machine.rs:208-228 (tree 0), :230-237 (tree 1)
@@ -646,43 +647,42 @@ static int prove_machine(nx_ctx* ctx, const nx_component_spec* comps, uint32_t n
             const nx_component_spec& c = comps[i];
             const uint32_t lo = local[i].first, hi = local[i].second, log = c.log_size, n_tree = groups[i].first;
             DevBuf slab;
+            const std::set<uint32_t> need = logup_needed_columns(c, tree);
+            DevBuf& kb = kept[tree][i]; ColMap& kp = kept_ptr[tree][i];
+            // One GPU: the columns the logup fractions read are produced IN their kept buffers (keep list) — filled there, or uploaded there as
+            // they arrive — and the commit's inverse transform reads them from there: the evaluations survive without being cloned
+            std::vector<std::pair<uint32_t, uint32_t*>> keep;
+            if (!D.on() && !need.empty()) {
+                H_TRY(kb.alloc(ctx, need.size() << log));
+                size_t q = 0;
+                for (uint32_t k : need) { uint32_t* dst = kb.p + (q++ << log); keep.push_back({k, dst}); kp[k] = dst; }
+            }
             if (host) H_TRY(slab.alloc(ctx, (size_t)n_tree << log));
             else if (hi > lo) {
                 H_TRY(slab.alloc(ctx, (size_t)(hi - lo) << log));
                 auto p = col_ptrs(slab.p, hi - lo, log);
+                if (!D.on()) for (auto& kv : keep) p[kv.first] = kv.second;            // lo == 0: the slab holds the whole group
                 H_TRY(synth_fill_range(ctx, c, i, tree, seed, 0, lo, hi - lo, p.data(), 0, 1u << log));
             }
-            const std::set<uint32_t> need = logup_needed_columns(c, tree);
-            DevBuf& kb = kept[tree][i]; ColMap& kp = kept_ptr[tree][i];
             if (host) {
-                // the columns the logup fractions read are cloned as they arrive (keep list); the slab is filled by the commit
-                std::vector<std::pair<uint32_t, uint32_t*>> keep;
-                if (!need.empty()) {
-                    H_TRY(kb.alloc(ctx, need.size() << log));
-                    size_t q = 0;
-                    for (uint32_t k : need) { uint32_t* dst = kb.p + (q++ << log); keep.push_back({k, dst}); kp[k] = dst; }
-                }
                 const uint32_t col0 = tree == 0 ? locs[i].pre0 : locs[i].main0;
                 const uint8_t* kinds = tree == 0 ? host->pre_kinds : host->main_kinds;
                 tb.extend_evals_host(std::move(slab), n_tree, log, (tree == 0 ? host->pre : host->main) + col0, kinds ? kinds + col0 : nullptr, host->coset_order, keep, col0,
                                      tree == 0 ? "nx_prove_machine_host_narrow: h_pre_cols (preprocessed trace)" : "nx_prove_machine_host_narrow: h_main_cols (main trace)");
                 continue;
             }
-            if (!need.empty()) {
-                if (D.on() && log < (uint32_t)D.log_w + 2) return set_err(ctx, NX_ERR_ARG, "row-sharded prove: every trace column needs at least 4 rows per GPU");
-                const uint64_t nb = D.on() ? D.block(log) : ((uint64_t)1 << log);
+            if (D.on() && !need.empty()) {               // row-sharded: the logup is row-wise, every GPU fills ITS ROWS of those columns
+                if (log < (uint32_t)D.log_w + 2) return set_err(ctx, NX_ERR_ARG, "row-sharded prove: every trace column needs at least 4 rows per GPU");
+                const uint64_t nb = D.block(log);
                 H_TRY(kb.alloc(ctx, need.size() * (size_t)nb));
                 size_t q = 0;
-                std::vector<uint32_t*> cd; std::vector<const uint32_t*> csrc;
                 for (uint32_t k : need) {
                     uint32_t* dst = kb.p + q * (size_t)nb;
-                    if (!D.on()) { cd.push_back(dst); csrc.push_back(slab.p + ((size_t)k << log)); }              // Column::clone (R4), batched below
-                    else { uint32_t* one[1] = {dst}; H_TRY(synth_fill_range(ctx, c, i, tree, seed, 0, k, 1, one, (uint32_t)D.begin(log), (uint32_t)nb)); }
+                    uint32_t* one[1] = {dst}; H_TRY(synth_fill_range(ctx, c, i, tree, seed, 0, k, 1, one, (uint32_t)D.begin(log), (uint32_t)nb));
                     kp[k] = dst; q++;
                 }
-                H_TRY(copy_columns(ctx, cd.data(), csrc.data(), (uint32_t)cd.size(), (size_t)nb));
             }
-            tb.extend_evals_local(std::move(slab), n_tree, log, lo, hi);
+            tb.extend_evals_local(std::move(slab), n_tree, log, lo, hi, keep);
         }
         return NX_OK;
     };

@@ -60,34 +60,84 @@ __device__ __forceinline__ void b2s_compress(u32 h[8], const u32 m[16], u32 t0, 
     h[4] ^= v4 ^ v12; h[5] ^= v5 ^ v13; h[6] ^= v6 ^ v14; h[7] ^= v7 ^ v15;
 }
 
-// 16 consecutive columns of one 64-byte message block at row i: the column addresses first (one uniform branch, wide scalar loads of
-// the pointer table), then 16 global loads issued back to back; columns past n_cols read as zero (the padded last block)
-__device__ __forceinline__ void load_block16(const ColSet& cols, u32 n_cols, u32 c0, u64 i, u32* dst) {
+// The 16 column addresses of the message block that starts at column c0 (every one of them inside the set): wave-uniform, so they live
+// in SGPRs — two wide scalar loads of the pointer table, or scalar arithmetic on base + stride.  TABLE is the kernel's template argument:
+// which form the set has is decided once per launch, not once per block.
+// The table is read through the constant address space (nothing writes it while the kernel runs): scalar loads whatever else the kernel does.
+typedef const u32* const __attribute__((address_space(4))) * ColTable;
+template <bool TABLE>
+__device__ __forceinline__ const u32* col_ptr(const ColSet& cols, u32 c) { return TABLE ? ((ColTable)(uintptr_t)cols.table)[c] : cols.base + (uint64_t)c * cols.stride; }
+template <bool TABLE>
+__device__ __forceinline__ void block_ptrs(const ColSet& cols, u32 c0, const u32** p) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) p[k] = col_ptr<TABLE>(cols, c0 + k);
+}
+// 16 global loads issued back to back; rows < 2^30: one 32-bit byte offset for all of them, the column bases stay in SGPRs
+// (`global_load_dword v, v_off, s[base:base+1]`).  The empty asm keeps the offset's zero-extension in the block of the loads: hoisted out of
+// the column loop as a 64-bit register pair it hides the form from instruction selection, and every load gets a v_lshl_add_u64 and
+// two VGPRs for its address (76 VGPRs and 6 waves per SIMD instead of 8).
+__device__ __forceinline__ void load_ptrs16(const u32* const* p, u32 off, u32* dst) {
+    asm volatile("" : "+v"(off));
+#pragma unroll
+    for (int k = 0; k < 16; k++) dst[k] = gld_off(p[k], off);
+}
+// the LAST block of a column set (starts at c0 = 16 * ((n_cols - 1) / 16)): full, or zero-padded past column n_cols
+template <bool TABLE>
+__device__ __forceinline__ void load_last_block(const ColSet& cols, u32 n_cols, u32 c0, u32 off, u32* dst) {
     const u32* p[16];
-    if (c0 + 16 <= n_cols) {
-        if (cols.table) {
-#pragma unroll
-            for (int k = 0; k < 16; k++) p[k] = cols.table[c0 + k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 16; k++) p[k] = cols.base + (uint64_t)(c0 + k) * cols.stride;
-        }
-        const u32 off = (u32)i << 2;          // rows < 2^30: one 32-bit byte offset for all 16 loads, the column bases stay in SGPRs
-#pragma unroll
-        for (int k = 0; k < 16; k++) dst[k] = gld_off(p[k], off);
+    if (c0 + 16 == n_cols) {
+        block_ptrs<TABLE>(cols, c0, p);
+        load_ptrs16(p, off, dst);
     } else {
-        const u32 off = (u32)i << 2;
 #pragma unroll
-        for (int k = 0; k < 16; k++) p[k] = cols.col(min(c0 + k, n_cols - 1));
+        for (int k = 0; k < 16; k++) p[k] = col_ptr<TABLE>(cols, min(c0 + k, n_cols - 1));
 #pragma unroll
         for (int k = 0; k < 16; k++) dst[k] = (c0 + k < n_cols) ? gld_off(p[k], off) : 0u;
     }
 }
 
+// Chain the n_cols >= 1 columns of a set into h, one 64-byte block per 16 columns, at the row whose byte offset is `off`.
+//   t: bytes hashed before the first of these blocks; the last block is compressed with (t_last, f_last), every other one with (t += 64, 0).
+// The blocks before the last are all full and none of them finalises, so the steady-state loop has no branch but its back edge.  Two
+// register sets A and B take turns as "being compressed" and "in flight" (the loop is unrolled by two; a single pair of named buffers costs
+// 16 v_mov per compression for the hand-over), and the column addresses of the block after next are requested BEFORE the compression, so
+// the scalar loads have the ~1000 VALU instructions of a compression to land in and the next block's global loads never wait for them.
+template <int MODE, bool TABLE>
+__device__ __forceinline__ void b2s_chain_columns(const ColSet& cols, u32 n_cols, u32 off, u32 h[8], u32 t, u32 t_last, u32 f_last) {
+    const u32 steady = (n_cols - 1) >> 4;                   // blocks before the last one
+    u32 A[16], B[16];
+    if (steady) {
+        const u32* pn[16];                                  // addresses of the next block to request
+        block_ptrs<TABLE>(cols, 0, pn);
+        load_ptrs16(pn, off, A);
+        block_ptrs<TABLE>(cols, 16 * min(1u, steady - 1), pn);
+        u32 j = 0;                                          // A holds block j; pn block min(j + 1, steady - 1)
+        for (; j + 2 < steady; j += 2) {
+            load_ptrs16(pn, off, B);
+            block_ptrs<TABLE>(cols, 16 * (j + 2), pn);
+            __builtin_amdgcn_sched_barrier(0);              // the address loads stay up here (left alone they sink to the end of the compression)
+            t += 64; b2s_compress(h, A, MODE == 0 ? t : 0u, 0);
+            load_ptrs16(pn, off, A);
+            block_ptrs<TABLE>(cols, 16 * min(j + 3, steady - 1), pn);
+            __builtin_amdgcn_sched_barrier(0);
+            t += 64; b2s_compress(h, B, MODE == 0 ? t : 0u, 0);
+        }
+        if (j + 2 == steady) {                              // an odd block left over: once per row, the hand-over by moves is free here
+            load_ptrs16(pn, off, B);
+            t += 64; b2s_compress(h, A, MODE == 0 ? t : 0u, 0);
+#pragma unroll
+            for (int k = 0; k < 16; k++) A[k] = B[k];
+        }
+    }
+    load_last_block<TABLE>(cols, n_cols, 16 * steady, off, B);
+    if (steady) { t += 64; b2s_compress(h, A, MODE == 0 ? t : 0u, 0); }
+    b2s_compress(h, B, MODE == 0 ? t_last : 0u, MODE == 0 ? f_last : 0u);
+}
+
 // One Merkle layer: node i = H(prev[2i] ‖ prev[2i+1] ‖ col_0[i] ‖ col_1[i] ‖ ...).
 //   MODE 0: standard Blake2s-256 (byte counter, final-block flag, IV ^ parameter block)
 //   MODE 1: zero-state raw compression chaining, t = f = 0, zero-padded 64-byte blocks
-template <int MODE>
+template <int MODE, bool TABLE>
 __global__ __launch_bounds__(256) void merkle_layer_kernel(ColSet cols, u32 n_cols, const u32* __restrict__ prev,
                                                            u32* __restrict__ out, u32 n_nodes) {
     u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -102,9 +152,9 @@ __global__ __launch_bounds__(256) void merkle_layer_kernel(ColSet cols, u32 n_co
         for (int k = 0; k < 8; k++) h[k] = 0;
     }
     const u32 total_bytes = (prev ? 64u : 0u) + 4u * n_cols;
-    u32 m[16];
     u32 t = 0;
     if (prev) {
+        u32 m[16];
         const u32* p = prev + (size_t)i * 16;
         uint4 a = gld4(p), b = gld4(p + 4), c = gld4(p + 8), d = gld4(p + 12);
         m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w; m[4] = b.x; m[5] = b.y; m[6] = b.z; m[7] = b.w;
@@ -113,23 +163,13 @@ __global__ __launch_bounds__(256) void merkle_layer_kernel(ColSet cols, u32 n_co
         if (MODE == 0) b2s_compress(h, m, t, n_cols == 0 ? 0xFFFFFFFFu : 0u);
         else b2s_compress(h, m, 0, 0);
     } else if (MODE == 0 && n_cols == 0) {
+        u32 m[16];
 #pragma unroll
         for (int k = 0; k < 16; k++) m[k] = 0;
         b2s_compress(h, m, 0, 0xFFFFFFFFu);  // Blake2s of the empty message
     }
-    // stream the columns 16 at a time, double-buffered: the 16 loads of chunk k+1 are in flight while the
-    // ~1000 VALU ops of chunk k's compression run
-    u32 nx_[16];
-    auto load_chunk = [&](u32 c0, u32* dst) { load_block16(cols, n_cols, c0, i, dst); };
-    if (n_cols) load_chunk(0, nx_);
-    for (u32 c0 = 0; c0 < n_cols; c0 += 16) {
-#pragma unroll
-        for (int k = 0; k < 16; k++) m[k] = nx_[k];
-        bool last = c0 + 16 >= n_cols;
-        if (!last) load_chunk(c0 + 16, nx_);
-        if (MODE == 0) { t = last ? total_bytes : t + 64; b2s_compress(h, m, t, last ? 0xFFFFFFFFu : 0u); }
-        else b2s_compress(h, m, 0, 0);
-    }
+    // stream the columns 16 at a time: the 16 loads of block k+1 are in flight while the ~1000 VALU ops of block k's compression run
+    if (n_cols) b2s_chain_columns<MODE, TABLE>(cols, n_cols, i << 2, h, t, total_bytes, 0xFFFFFFFFu);
     uint4* o = reinterpret_cast<uint4*>(out + (size_t)i * 8);
     o[0] = make_uint4(h[0], h[1], h[2], h[3]);
     o[1] = make_uint4(h[4], h[5], h[6], h[7]);
@@ -210,7 +250,7 @@ __global__ __launch_bounds__(256) void merkle_reduce_kernel(const u32* __restric
 
 // One column shard of a leaf layer: continue (or start) the per-row chaining state over this shard's columns.
 // `first`: the shard starts at column 0 (state = IV); `last`: it holds the layer's last column (finalisation).
-template <int MODE>
+template <int MODE, bool TABLE>
 __global__ __launch_bounds__(256) void merkle_leaf_chain_kernel(ColSet cols, u32 n_cols, u32 col_offset, u32 total_cols,
                                                                 const u32* __restrict__ state_in, u32* __restrict__ state_out,
                                                                 u64 row_begin, u64 n_rows) {
@@ -231,20 +271,9 @@ __global__ __launch_bounds__(256) void merkle_leaf_chain_kernel(ColSet cols, u32
 #pragma unroll
         for (int k = 0; k < 8; k++) h[k] = 0;
     }
-    const u32 total_bytes = 4u * total_cols;
-    u32 t = 4u * col_offset;   // bytes hashed by the previous shards
-    u32 m[16], nx_[16];
-    auto load_chunk = [&](u32 c0, u32* dst) { load_block16(cols, n_cols, c0, i, dst); };
-    if (n_cols) load_chunk(0, nx_);
-    for (u32 c0 = 0; c0 < n_cols; c0 += 16) {
-#pragma unroll
-        for (int k = 0; k < 16; k++) m[k] = nx_[k];
-        const bool last_chunk = c0 + 16 >= n_cols;
-        if (!last_chunk) load_chunk(c0 + 16, nx_);
-        const bool fin = last_chunk && last_shard;
-        if (MODE == 0) { t = fin ? total_bytes : t + 64; b2s_compress(h, m, t, fin ? 0xFFFFFFFFu : 0u); }
-        else b2s_compress(h, m, 0, 0);
-    }
+    // t: bytes hashed by the previous shards; only the layer's last shard finalises
+    b2s_chain_columns<MODE, TABLE>(cols, n_cols, (u32)i << 2, h, 4u * col_offset, last_shard ? 4u * total_cols : 4u * col_offset + 64u * ((n_cols + 15) >> 4),
+                                   last_shard ? 0xFFFFFFFFu : 0u);
     uint4* o = reinterpret_cast<uint4*>(state_out + r * 8);
     o[0] = make_uint4(h[0], h[1], h[2], h[3]);
     o[1] = make_uint4(h[4], h[5], h[6], h[7]);
@@ -735,10 +764,12 @@ int leaf_chain_launch(nx_ctx* ctx, ColSet cs, u32 n_cols, u32 col_offset, u32 to
     KTimer timer(ctx, NX_T_MERKLE, n_rows * (4ull * n_cols + 64));
     dim3 block(256);
     dim3 grid((unsigned)((n_rows + 255) / 256));
-    if (ctx->hash_mode == NX_HASH_BLAKE2S)
-        hipLaunchKernelGGL(merkle_leaf_chain_kernel<0>, grid, block, 0, ctx->stream, cs, n_cols, col_offset, total_cols, state_in, state_out, row_begin, n_rows);
-    else
-        hipLaunchKernelGGL(merkle_leaf_chain_kernel<1>, grid, block, 0, ctx->stream, cs, n_cols, col_offset, total_cols, state_in, state_out, row_begin, n_rows);
+    // hash mode and the set's form (pointer table or base + stride) pick the instantiation: neither is looked at again inside the kernel
+#define NX_LEAF(M, T) hipLaunchKernelGGL((merkle_leaf_chain_kernel<M, T>), grid, block, 0, ctx->stream, cs, n_cols, col_offset, total_cols, state_in, state_out, row_begin, n_rows)
+    const bool std_hash = ctx->hash_mode == NX_HASH_BLAKE2S;
+    if (cs.table) { if (std_hash) NX_LEAF(0, true); else NX_LEAF(1, true); }
+    else { if (std_hash) NX_LEAF(0, false); else NX_LEAF(1, false); }
+#undef NX_LEAF
     NX_LAUNCH_CHECK(ctx);
     return NX_OK;
 }
@@ -933,8 +964,11 @@ int reduce_to_root(nx_ctx* ctx, u32* a, u32* b, uint32_t max_log, const std::vec
 int merkle_layer(nx_ctx* ctx, ColSet cols, u32 n_cols, const u32* prev, u32* out, u32 log) {
     u32 n = 1u << log;
     dim3 grid((n + 255) / 256), block(256);
-    if (ctx->hash_mode == NX_HASH_BLAKE2S) hipLaunchKernelGGL(merkle_layer_kernel<0>, grid, block, 0, ctx->stream, cols, n_cols, prev, out, n);
-    else hipLaunchKernelGGL(merkle_layer_kernel<1>, grid, block, 0, ctx->stream, cols, n_cols, prev, out, n);
+#define NX_LAYER(M, T) hipLaunchKernelGGL((merkle_layer_kernel<M, T>), grid, block, 0, ctx->stream, cols, n_cols, prev, out, n)
+    const bool std_hash = ctx->hash_mode == NX_HASH_BLAKE2S;
+    if (cols.table) { if (std_hash) NX_LAYER(0, true); else NX_LAYER(1, true); }
+    else { if (std_hash) NX_LAYER(0, false); else NX_LAYER(1, false); }
+#undef NX_LAYER
     NX_LAUNCH_CHECK(ctx);
     return NX_OK;
 }

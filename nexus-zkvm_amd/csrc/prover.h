@@ -165,7 +165,9 @@ class TreeBuilder {
         // the element kind of each host column (NX_COL_*, empty = all NX_COL_U32), its index in the caller's array (a refusal names it) and
         // the caller's name of that array
         std::vector<uint8_t> kinds; uint32_t call_col0 = 0; const char* what = nullptr;
-        std::vector<std::pair<uint32_t, uint32_t*>> keep;                    // (column of the group, device buffer): its evaluations, cloned before the transform (R4)
+        // (column of the group, device buffer): the column's evaluations are (device fill) or arrive (host feed) in that buffer, not in the slab,
+        // and stay there: the inverse transform reads them from it and writes the coefficients to the slab (the reference's trace clone, R4, without a copy)
+        std::vector<std::pair<uint32_t, uint32_t*>> keep;
     };
     explicit TreeBuilder(CommitmentSchemeProver& c) : cs(c) {}
     // slab: n_cols contiguous columns of 2^log words (bit-reversed evaluations on CanonicCoset(log).circle_domain())
@@ -174,7 +176,7 @@ class TreeBuilder {
     // uploads it in column chunks on the copy stream — pinned in place, R3's permutation on the device when coset_order — and runs each
     // chunk's iFFT + LDE as soon as the chunk has arrived, so the PCIe transfer and the transforms overlap (one GPU).  kinds: the element
     // kind of each host column (NX_COL_*, null = all NX_COL_U32; nx::HostFeed::chunk).  keep: columns whose evaluations are needed after the
-    // commit (the logup fractions read them): cloned on arrival, the reference's trace clone (machine.rs:232).  call_col0 / what: where the
+    // commit (the logup fractions read them): uploaded into the keep buffer, the reference's trace clone (machine.rs:232).  call_col0 / what: where the
     // group's columns start in the caller's array and its name, for the refusal's message
     void extend_evals_host(DevBuf&& slab, uint32_t n_cols, uint32_t log, const void* const* h_cols, const uint8_t* kinds, int coset_order,
                            const std::vector<std::pair<uint32_t, uint32_t*>>& keep, uint32_t call_col0, const char* what) {
@@ -184,8 +186,12 @@ class TreeBuilder {
         if (kinds) g.kinds.assign(kinds, kinds + n_cols);
         g.call_col0 = call_col0; g.what = what;
     }
-    // row-sharded prove: the slab holds this GPU's columns [lo, hi) of the group (plan_local_columns)
-    void extend_evals_local(DevBuf&& slab, uint32_t n_cols, uint32_t log, uint32_t lo, uint32_t hi) { push(std::move(slab), n_cols, log, true, lo, hi); }
+    // row-sharded prove: the slab holds this GPU's columns [lo, hi) of the group (plan_local_columns).  keep (one GPU only): columns whose
+    // evaluations the caller filled into buffers of their own (Group::keep) instead of the slab
+    void extend_evals_local(DevBuf&& slab, uint32_t n_cols, uint32_t log, uint32_t lo, uint32_t hi, const std::vector<std::pair<uint32_t, uint32_t*>>& keep = {}) {
+        push(std::move(slab), n_cols, log, true, lo, hi);
+        groups.back().keep = keep;
+    }
     // coefficients, all n_cols of them on every GPU (the composition polynomial)
     void extend_polys(DevBuf&& slab, uint32_t n_cols, uint32_t log) { push(std::move(slab), n_cols, log, false, 0, n_cols); }
     int commit(Blake2sChannel& channel) { int rc = commit_begin(); return rc != NX_OK ? rc : commit_end(channel); }

@@ -241,6 +241,25 @@ void plan_local_columns(const std::vector<std::pair<uint32_t, uint32_t>>& groups
 // Blake2s chain per row over the largest columns in commit order, so it is built incrementally: as soon as a run of columns is
 // extended, its 16-column blocks are absorbed, in stream order (tree_pipe_* in merkle.hip).
 
+// nx_lde_batch whose column k's evaluations are in src[k]: its coefficients go to cols[k], its extension to lde[k], and where src[k] is
+// another buffer than cols[k] the evaluations survive there (what the reference clones the trace for, R4: the logup fractions read them
+// after the commit) without a copy — the inverse transform's first pass reads one buffer and writes the other.  Sizes that are
+// transformed in place (below 2^14 rows, other blow-ups) get the evaluations copied into cols first.
+static int lde_batch_from(nx_ctx* ctx, const nx_twiddles* tw, const uint32_t* const* src, uint32_t* const* cols, uint32_t n_cols, uint32_t log, uint32_t log_blowup,
+                          uint32_t* const* lde) {
+    if (n_cols == 0) return NX_OK;
+    std::vector<uint32_t*> cd; std::vector<const uint32_t*> csrc;
+    for (uint32_t k = 0; k < n_cols; k++) if (src[k] != cols[k]) { cd.push_back(cols[k]); csrc.push_back(src[k]); }
+    const bool from = !cd.empty() && nx::fft_lde_reads_source(ctx, log, log_blowup);
+    if (!cd.empty() && !from) H_TRY(nx::copy_columns(ctx, cd.data(), csrc.data(), (uint32_t)cd.size(), (size_t)1 << log));
+    nx::ColSet c, o;
+    H_TRY(nx::make_colset(ctx, (const uint32_t* const*)cols, n_cols, &c));
+    H_TRY(nx::make_colset(ctx, (const uint32_t* const*)lde, n_cols, &o));
+    nx::ColSet s = c;                                                  // in place unless a column's evaluations are elsewhere
+    if (from) H_TRY(nx::make_colset(ctx, src, n_cols, &s));
+    return nx::fft_lde_from(ctx, tw, s, c, n_cols, log, log_blowup, o);
+}
+
 int TreeBuilder::commit_end(Blake2sChannel& channel) {
     if (cs.dist.on()) return commit_dist(channel);
     nx_ctx* ctx = cs.ctx;
@@ -284,8 +303,9 @@ int TreeBuilder::commit_begin() {
             for (size_t g = g0; g < g1; g++) { auto p = col_ptrs(groups[g].slab.p, groups[g].n_cols, log); in.insert(in.end(), p.begin(), p.end()); }
             auto out = col_ptrs(lde.p, n_run, el);
             const bool leaf = el == max_el;
-            // host-resident columns of this run: per column its host source, and what to clone on arrival
-            std::vector<const void*> hsrc(n_run, nullptr); std::vector<uint32_t*> keep_of(n_run, nullptr);
+            // host-resident columns of this run: per column its host source; src: where a column's evaluations are — its slab column, or the
+            // buffer that keeps them past the commit (Group::keep): the producer wrote (the host feed writes) that buffer instead
+            std::vector<const void*> hsrc(n_run, nullptr); std::vector<uint32_t*> src(in);
             std::vector<uint8_t> hkind(n_run, (uint8_t)NX_COL_U32); std::vector<uint32_t> hcall(n_run, 0);
             bool any_host = false; int coset_order = 0; const char* what = nullptr;
             {
@@ -298,8 +318,8 @@ int TreeBuilder::commit_begin() {
                         for (uint32_t k = 0; k < groups[g].n_cols; k++) hcall[off + k] = groups[g].call_col0 + k;
                         if (!groups[g].kinds.empty()) std::copy(groups[g].kinds.begin(), groups[g].kinds.end(), hkind.begin() + off);
                         if (groups[g].what) what = groups[g].what;
-                        for (auto& kv : groups[g].keep) { if (kv.first >= groups[g].n_cols) return set_err(ctx, NX_ERR_ARG, "TreeBuilder: keep index outside the group"); keep_of[off + kv.first] = kv.second; }
                     }
+                    for (auto& kv : groups[g].keep) { if (kv.first >= groups[g].n_cols) return set_err(ctx, NX_ERR_ARG, "TreeBuilder: keep index outside the group"); src[off + kv.first] = kv.second; }
                     off += groups[g].n_cols;
                 }
             }
@@ -316,13 +336,12 @@ int TreeBuilder::commit_begin() {
                         if (!hsrc[a]) { a++; continue; }
                         uint32_t b2 = a; while (b2 < c0 + nb && hsrc[b2]) b2++;
                         hipEvent_t ready = nullptr;
-                        H_TRY(feed->chunk(hsrc.data() + a, hkind.data() + a, hcall.data() + a, what, in.data() + a, b2 - a, &ready));
+                        H_TRY(feed->chunk(hsrc.data() + a, hkind.data() + a, hcall.data() + a, what, src.data() + a, b2 - a, &ready));
                         NX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ready, 0));
                         a = b2;
                     }
-                    for (uint32_t a = c0; a < c0 + nb; a++) if (keep_of[a]) H_TRY(nx_copy(ctx, keep_of[a], in[a], (size_t)1 << log));       // Column::clone (R4)
                 }
-                if (is_evals) H_TRY(nx_lde_batch(ctx, cs.tw, in.data() + c0, nb, log, cs.cfg.log_blowup, out.data() + c0));   // K3 + K4
+                if (is_evals) H_TRY(lde_batch_from(ctx, cs.tw, (const uint32_t* const*)src.data() + c0, in.data() + c0, nb, log, cs.cfg.log_blowup, out.data() + c0));   // K3 + K4
                 else H_TRY(nx_evaluate_batch(ctx, cs.tw, (const uint32_t* const*)in.data() + c0, nb, log, cs.cfg.log_blowup, out.data() + c0));  // K4
                 if (leaf) H_TRY(tree_pipe_absorb(ctx, &tp, (const uint32_t* const*)out.data() + c0, nb, false));                   // K5, leaf layer (16-column blocks as they complete)
             }
@@ -1768,11 +1787,7 @@ extern "C" {
 int nx_lde_batch(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, uint32_t n_cols, uint32_t log_size, uint32_t log_blowup,
                  uint32_t* const* d_lde) {
     NX_GUARD(ctx);
-    if (n_cols == 0) return NX_OK;
-    ColSet c, o;
-    NX_TRY(make_colset(ctx, d_cols, n_cols, &c));
-    NX_TRY(make_colset(ctx, d_lde, n_cols, &o));
-    return fft_lde(ctx, tw, c, n_cols, log_size, log_blowup, o);
+    return nxhip::lde_batch_from(ctx, tw, (const uint32_t* const*)d_cols, d_cols, n_cols, log_size, log_blowup, d_lde);   // in place
 }
 
 int nx_lde_commit(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, uint32_t n_cols, uint32_t log_size, uint32_t log_blowup,
