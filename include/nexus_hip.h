@@ -83,7 +83,9 @@ int nx_ctx_set_hash_mode(nx_ctx* ctx, int mode);
  * above it), "fri.device_channel", "fri.tail" (0 = off, 1 = the FRI layers of <= 2^11 points in one launch,
  * 2..11 = from 2^that many points), "logup.scan_tiled", "logup.per_column", "merkle.fused" (0..31, default 21; 0 = off, else the smallest log size from which a tree of <= 4 columns of one
  * size gets its leaf hash and 6 levels in one launch), "machine.logup_program" (default 0; 1: nx_prove_machine builds every wide-tuple component's interaction
- * trace through nx_logup_program), "trace.vec4" (1, the default: nx_trace_program runs a program whose loads all have offset 0 with four
+ * trace through nx_logup_program), "machine.reuse_preprocessed" (default 0: every proof commits its preprocessed tree afresh, as the
+ * reference does; 1: nx_prove_machine keeps the committed preprocessed tree of a statement shape in the context and adopts it in later
+ * proofs of that shape — nx_prover_tree_adopt's rule; statements with a table component still fill theirs), "trace.vec4" (1, the default: nx_trace_program runs a program whose loads all have offset 0 with four
  * storage positions per lane — 16-byte loads and stores — instead of one row per lane).  "host.pack_threads" (1..64; default
  * min(16, hardware threads)): host threads that pack NX_COL_U32_AS_U16 / NX_COL_U32_AS_U8 columns of the narrow upload entry points.
  * Unknown names and out-of-range values are NX_ERR_ARG.

@@ -76,9 +76,10 @@ def test_interpolate_evaluate_match_oracle(be, oracle, log):
 
 @pytest.mark.parametrize("log", [13, 14, 15, 16, 17, 18, 19, 20, 21, 22])
 def test_fused_lde_matches_oracle_at_every_pass_shape(be, oracle, log):
-    """nx_lde_batch with blow-up 2 takes the fused-middle route from 2^14 rows up (lde_mid_kernel with 1..7 layers here, 8 and 9 in
-    the large-transform test, the 3-pass plan at 2^23): coefficients and every LDE value against the oracle, an odd column count so
-    the batch tail is exercised too."""
+    """nx_lde_batch with blow-up 2 takes the fused-middle route from 2^14 rows up: lde_mid_kernel with 1..9 layers here, always as the
+    two-pass plan (first pass + middle launch).  Plans of three and more passes — inverse passes before the middle launch, forward
+    passes after it — and the 10- and 11-layer middle launch are compared in test_gpu_options.py; the large-transform test below never
+    calls nx_lde_batch.  Coefficients and every LDE value against the oracle, an odd column count."""
     n_cols = 3
     vals = rand_cols(700 + log, n_cols, log)
     tw = be.precompute_twiddles(log)
@@ -111,10 +112,10 @@ def test_context_options_are_per_context_and_validated(nz):
 
 @pytest.mark.parametrize("log", [21, 22, 23, 24])
 def test_large_transforms_match_oracle_and_roundtrip(be, oracle, log):
-    """2-pass schedules of the wide kernel — 2^13-row tiles (13+8, 13+9 layers) up to 2^22 points, 2^14-row tiles (14+9, 14+10, 14+11)
-    from 2^23 points (round 4: the third pass is gone) —: one column against the oracle, the others through interpolate∘evaluate = id
-    and LDE-restricted-to-the-trace-domain properties.  log 23 / 24 run interpolate, evaluate and the inverse of the extension at
-    2^23 ... 2^25 points, i.e. every 2^14-tile kernel (FIRST and K = 9, 10, 11, forward and inverse)."""
+    """The default plans of plan13 (csrc/fft13.hip: 2^13-row tiles, the first 13 layers, then passes of at most "fft.kmax" = 9 layers)
+    at 2^21 .. 2^25 points — 13+8 and 13+9 layers up to 2^22 points, three passes from 2^23 (13+5+5, 13+6+5, 13+6+6) —: one column
+    against the oracle, the others through interpolate∘evaluate = id and LDE-restricted-to-the-trace-domain properties.  log 23 / 24 run
+    interpolate, evaluate and the inverse of the extension at 2^23 ... 2^25 points (nx_interpolate_batch / nx_evaluate_batch only)."""
     n_cols = 3
     tw = be.precompute_twiddles(log + 1)
     otw = oracle.Twiddles(log + 1)
