@@ -350,7 +350,12 @@ int nx_synth_fill_tree(nx_ctx* ctx, const nx_component_spec* comps, uint32_t n_c
 
 /* Full prove of the synthetic machine: the orchestration of reference prover/src/machine.rs:184-296
  * and stwo::prover::prove on device.  Returns a malloc'd proof in the flat "NXP1" u32 wire format
- * (free with nx_free_host). stats may be NULL. */
+ * (free with nx_free_host). stats may be NULL.
+ * SIZES.  The argument check admits 1 <= log_size <= 28, but a statement PROVES only if its smallest component has
+ * log_size >= log_last_layer_degree_bound + 2 — with the default bound of 0: at least four rows.  Below that the component's
+ * quotient column is no larger than FRI's last layer and never folds into a line: the prove runs up to the FRI commit phase and then
+ * returns NX_ERR_PROTOCOL ("fri: first-layer columns not consumed"), as Stwo's FriProver does; nothing stays allocated and the context
+ * remains usable.  The same holds for nx_prove_machine, nx_prove_machine_host and nx_prover_prove. */
 int nx_prove_synth(nx_ctx* ctx, const nx_component_spec* comps, uint32_t n_comps, const nx_pcs_config* cfg,
                    uint64_t seed, const uint8_t* ad, size_t ad_len, uint32_t** proof_words, size_t* n_words,
                    nx_prove_stats* stats);

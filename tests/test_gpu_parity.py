@@ -1000,6 +1000,11 @@ def test_session_proves_the_recorded_synthetic_machine_identically(be, nz, oracl
 def test_session_logup_air_matches_the_oracle_session(be, nz, oracle, logs, lcd, bounds, hd):
     """A multi-component AIR with a secure logup column at offsets [-1, 0] and lookup elements drawn from the session's
     channel: same draws, same roots, same proof bytes as the CPU oracle's session, and the oracle's verifier accepts."""
+    check_session_logup_air(be, nz, oracle, logs, lcd, bounds, hd)
+
+
+def check_session_logup_air(be, nz, oracle, logs, lcd=1, bounds=None, hd=False):
+    """The body of the test above (tests/test_gpu_size_lattice.py runs it down to 4-row traces)."""
     from test_prover_session_cpu import build_mixed_air
     ocfg = oracle.default_cfg(pow_bits=2, log_constraint_degree=lcd, log_blowup=lcd)
     cfg = _hip_cfg(nz, ocfg)
