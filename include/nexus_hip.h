@@ -498,7 +498,10 @@ int nx_m31_narrow(nx_ctx* ctx, uint32_t* d_dst, const uint64_t* d_src, size_t n_
  * program over the field tower, and that can.  Registers are indices of a per-row register file (a secure-field value takes
  * 4 consecutive registers); the host allocates them.  For every row of the evaluation domain (bit-reversed circle-domain
  * order, log size log_eval) the program runs once and  acc[row] += (sum_j alpha_powers[j] * C_j(row)) * denom_inv[row >> log_size]
- * (FrameworkComponent::evaluate_constraint_quotients_on_domain). */
+ * (FrameworkComponent::evaluate_constraint_quotients_on_domain).
+ * Row offsets (NX_C_LOAD, NX_C_LOADE): any int32 is allowed and is taken modulo the trace length 2^log_size — row + b trace steps is
+ * natural trace row (i + b) mod 2^log_size, on every evaluation domain.  Tested on the device against the oracle at offsets beyond
+ * +-1, of the trace length and more, and at INT32_MIN / INT32_MAX (tests/test_gpu_wide_masks.py). */
 enum {
     NX_C_LOAD = 0,          /* B[dst] = cols[a][row + (int32)b trace steps]                          */
     NX_C_CONST = 1,         /* B[dst] = a (canonical M31 immediate)                                  */
@@ -640,7 +643,10 @@ void nx_committed_tree_release(nx_committed_tree* tree);
 /* A component: what FrameworkComponent<E> is to Stwo (reference prover/src/components/mod.rs:15-57).  Column k of the program is
  * column col_index[k] of tree col_tree[k] (TraceLocationAllocator); it is sampled at the mask_count[k] row offsets listed next in
  * mask_offsets (InfoEvaluator, components/mod.rs:59-67) — every LOAD offset must be listed, every committed column must be
- * claimed by some component.  kernel: the program compiled by nx_air_compile, or NULL to let nx_prover_prove compile it. */
+ * claimed by some component.  kernel: the program compiled by nx_air_compile, or NULL to let nx_prover_prove compile it.
+ * A mask offset is any int32, taken modulo the trace length: the column is sampled at the OODS point + offset trace steps.  Two entries
+ * of one column that coincide modulo the length are sampled twice at the same point (two equal values in the proof, one quotient batch
+ * holding the column twice); tested with the rest of the wide offsets (tests/test_gpu_wide_masks.py). */
 typedef struct {
     uint32_t log_size;
     const nx_cinstr* program; uint32_t n_instr, n_regs;

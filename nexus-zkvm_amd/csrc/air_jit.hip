@@ -282,7 +282,7 @@ static std::string generate_kernel(const nx_cinstr* prog, const std::vector<uint
     std::vector<int> offs;
     for (uint32_t i : keep)
         if (prog[i].op == NX_C_LOAD || prog[i].op == NX_C_LOADE) { int o = (int)prog[i].b; if (std::find(offs.begin(), offs.end(), o) == offs.end()) offs.push_back(o); }
-    auto off_name = [](int o) { return std::string("row_") + (o < 0 ? "m" : "p") + std::to_string(o < 0 ? -o : o); };
+    auto off_name = [](int o) { return std::string("row_") + (o < 0 ? "m" : "p") + std::to_string(o < 0 ? -(int64_t)o : (int64_t)o); };   // INT_MIN has no int negation
     for (int o : offs)
         s += "  const u32 " + off_name(o) + (check ? " = trace_row_offset(r, log_size, " : " = row_offset(r, log_size, e, ") + std::to_string(o) + ");\n";
     for (uint32_t k = 0; k < n_regs; k++) s += (k % 16 == 0 ? std::string("  u32 ") : std::string(", ")) + "r" + std::to_string(k) + ((k % 16 == 15 || k + 1 == n_regs) ? " = 0;\n" : " = 0");
@@ -1014,7 +1014,7 @@ static std::string generate_logup_kernel(const nx_cinstr* prog, const std::vecto
     std::vector<int> offs;
     for (uint32_t i : keep)
         if (prog[i].op == NX_C_LOAD || prog[i].op == NX_C_LOADE) { int o = (int)prog[i].b; if (std::find(offs.begin(), offs.end(), o) == offs.end()) offs.push_back(o); }
-    auto off_name = [](int o) { return std::string("row_") + (o < 0 ? "m" : "p") + std::to_string(o < 0 ? -o : o); };
+    auto off_name = [](int o) { return std::string("row_") + (o < 0 ? "m" : "p") + std::to_string(o < 0 ? -(int64_t)o : (int64_t)o); };   // INT_MIN has no int negation
     for (int o : offs) s += "  const u32 " + off_name(o) + " = trace_row_offset(r, log_size, " + std::to_string(o) + ");\n";
     for (uint32_t k = 0; k < n_regs; k++) s += (k % 16 == 0 ? std::string("  u32 ") : std::string(", ")) + "r" + std::to_string(k) + ((k % 16 == 15 || k + 1 == n_regs) ? " = 0;\n" : " = 0");
     auto R = [](uint32_t i) { return "r" + std::to_string(i); };
@@ -1496,8 +1496,8 @@ static std::string generate_trace_kernel(const nx_cinstr* prog, const std::vecto
         if (std::find(offs.begin(), offs.end(), o) == offs.end()) offs.push_back(o);
         if (std::find(loads.begin(), loads.end(), std::make_pair(prog[i].a, o)) == loads.end()) loads.push_back({prog[i].a, o});
     }
-    auto off_name = [](int o) { return std::string("row_") + (o < 0 ? "m" : "p") + std::to_string(o < 0 ? -o : o); };
-    auto ld_name = [](uint32_t c, int o) { return "l" + std::to_string(c) + (o < 0 ? "m" : "p") + std::to_string(o < 0 ? -o : o); };
+    auto off_name = [](int o) { return std::string("row_") + (o < 0 ? "m" : "p") + std::to_string(o < 0 ? -(int64_t)o : (int64_t)o); };   // INT_MIN has no int negation
+    auto ld_name = [](uint32_t c, int o) { return "l" + std::to_string(c) + (o < 0 ? "m" : "p") + std::to_string(o < 0 ? -(int64_t)o : (int64_t)o); };   // INT_MIN has no int negation
     if (vec4) {
         for (const auto& l : loads) s += "  const v4u " + ld_name(l.first, 0) + " = G4(cols[" + std::to_string(l.first) + "])[q];\n";
         // a column some store writes under a flag keeps its content where the flag is 0: the lane starts from the stored words
