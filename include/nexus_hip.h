@@ -991,6 +991,36 @@ int nx_trace_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_instr, ui
 int nx_trace_keccak_round(nx_ctx* ctx, const uint64_t* d_states, uint32_t n_instances, uint32_t first_round, uint32_t log_rounds,
                           uint32_t log_size, uint32_t* const* d_main, uint32_t* const* d_pre, uint64_t* d_states_out);
 
+/* ------------------------------------------- the keccak memory-check trace filled on the device from the instances' inputs ----------
+ * The reference's PermutationMemoryCheck component (prover/src/extensions/keccak/memory_check/trace.rs:32-123) hands the input state to
+ * the first KeccakRound component, takes the output state back from the second and charges the 200 byte accesses of every call to the
+ * load/store memory argument: 2001 main columns, computed on the CPU with a full keccakf per row.  The device needs the 1004 bytes of
+ * an instance: its state, one address and 200 timestamps.
+ * d_states: n_instances x 25 little-endian 64-bit lanes (the first round component's d_states); d_addresses: n_instances words
+ * (KeccakSideNote::addresses); d_timestamps: n_instances x 200 words, instance-major (KeccakSideNote::timestamps[row][byte]), 16-byte
+ * aligned (a work-item reads its 800 bytes as 16-byte loads).  Each may be NULL when n_instances == 0.  Natural trace row r is instance
+ * r.  Rows r >= n_instances are padding: every column is 0 on them except is_padding, which is 1 (out_state too: it is NOT keccak-f of
+ * the zero state, trace.rs:41 writes the real rows only).
+ * d_main: NX_KECCAK_MEMCHECK_MAIN_COLS device columns of 2^log_size words, TRACE-DOMAIN EVALUATIONS in bit-reversed circle-domain order
+ * (the rule of nx_trace_keccak_round), in the order of trace.rs:34: the 200 input-state bytes (lane l, byte b at 8 l + b); the 200
+ * output-state bytes, keccak-f[1600] of the input; 400 address limbs, for i in 0..200 the low 16 bits of addr + i, then the high 16;
+ * 400 previous-timestamp limbs, low then high of ts[i]; 400 next-timestamp limbs, of ts[i] + 1; 200 address carries,
+ * ((addr + i) & 0xFFFF) == 0xFFFF; 200 timestamp carries, (ts[i] & 0xFFFF) == 0xFFFF; is_padding.
+ * addr + i and ts[i] + 1 are taken MODULO 2^32: an address above 2^32 - 200 or a timestamp of 2^32 - 1 gives columns that do not
+ * satisfy the component's constraints, and nx_prover_check names the row; the call validates nothing that lies in device memory.
+ * d_pre: NULL, or NX_KECCAK_MEMCHECK_PRE_COLS column: is_last, 1 at natural row 2^log_size - 1, else 0.
+ * d_states_out: NULL, or n_instances x 25 lanes: the permuted states, equal to the second round component's d_states_out.
+ * Exact integers: the same words on every run.  One work-item per storage position.  Stream-ordered like nx_trace_keccak_round; no
+ * device memory is allocated, the pointer table travels through the context's staging ring.
+ * NX_ERR_ARG (nx_last_error names the argument; nothing is launched): log_size outside 1..30; n_instances > 2^log_size; a NULL or
+ * repeated column pointer, a pointer shared between d_main and d_pre; d_states, d_addresses or d_timestamps NULL with n_instances > 0;
+ * d_states or d_states_out not 8-byte aligned; d_timestamps not 16-byte aligned; d_states_out overlapping d_states; a NULL ctx. */
+#define NX_KECCAK_MEMCHECK_MAIN_COLS 2001   /* 2 x 200 state bytes, 3 x 400 limbs, 2 x 200 carries, is_padding */
+#define NX_KECCAK_MEMCHECK_PRE_COLS  1      /* is_last */
+int nx_trace_keccak_memory_check(nx_ctx* ctx, const uint64_t* d_states, const uint32_t* d_addresses, const uint32_t* d_timestamps,
+                                 uint32_t n_instances, uint32_t log_size, uint32_t* const* d_main, uint32_t* const* d_pre,
+                                 uint64_t* d_states_out);
+
 /* Config #2: LDE + Blake2s commit of n_cols random columns of 2^log_size rows (already resident,
  * bit-reversed evaluations, overwritten by their coefficients); d_lde receives the LDE columns. */
 int nx_lde_commit(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, uint32_t n_cols, uint32_t log_size,

@@ -644,6 +644,7 @@ class AccessSummary(C.Structure):
 
 MULT_LDS_MAX_KEY_BITS = 12   # NX_MULT_LDS_MAX_KEY_BITS: widest key space nx_logup_multiplicities counts in LDS
 KECCAK_ROUND_MAIN_COLS, KECCAK_ROUND_PRE_COLS = 1705, 9   # NX_KECCAK_ROUND_MAIN_COLS, NX_KECCAK_ROUND_PRE_COLS
+KECCAK_MEMCHECK_MAIN_COLS, KECCAK_MEMCHECK_PRE_COLS = 2001, 1   # NX_KECCAK_MEMCHECK_MAIN_COLS, NX_KECCAK_MEMCHECK_PRE_COLS
 
 
 class ProveStats(C.Structure):
@@ -1382,6 +1383,22 @@ class HipBackend:
         pp = (C.c_void_p * KECCAK_ROUND_PRE_COLS)(*[int(x) if x else None for x in pre_ptrs]) if pre_ptrs is not None else None
         self._chk(self.L.nx_trace_keccak_round(self.ctx, C.c_void_p(int(states_ptr)) if states_ptr else None, C.c_uint32(int(n_instances)), C.c_uint32(int(first_round)),
                                                C.c_uint32(int(log_rounds)), C.c_uint32(int(log_size)), mp, pp, C.c_void_p(int(states_out_ptr)) if states_out_ptr else None))
+
+    def trace_keccak_memory_check(self, states_ptr, addresses_ptr, timestamps_ptr, n_instances, log_size, main_ptrs, pre_ptrs=None, states_out_ptr=None):
+        """nx_trace_keccak_memory_check: the PermutationMemoryCheck component's trace filled on the device.  states_ptr: device address of
+        n_instances x 25 64-bit lanes, addresses_ptr: n_instances words, timestamps_ptr: n_instances x 200 words, 16-byte aligned (each
+        None when n_instances is 0); natural row r is instance r.  main_ptrs: KECCAK_MEMCHECK_MAIN_COLS device addresses of 2^log_size
+        words, e.g. what ProverSession.tree_begin handed out; pre_ptrs: None or the one is_last column; states_out_ptr: None or
+        n_instances x 25 lanes, keccak-f[1600] of the inputs.  addr + i and ts + 1 are taken modulo 2^32.  Stream-ordered."""
+        if len(main_ptrs) != KECCAK_MEMCHECK_MAIN_COLS:
+            raise NexusHipError(f"trace_keccak_memory_check: {len(main_ptrs)} main columns, {KECCAK_MEMCHECK_MAIN_COLS} expected")
+        if pre_ptrs is not None and len(pre_ptrs) != KECCAK_MEMCHECK_PRE_COLS:
+            raise NexusHipError(f"trace_keccak_memory_check: {len(pre_ptrs)} preprocessed columns, {KECCAK_MEMCHECK_PRE_COLS} expected")
+        mp = (C.c_void_p * KECCAK_MEMCHECK_MAIN_COLS)(*[int(x) if x else None for x in main_ptrs])
+        pp = (C.c_void_p * KECCAK_MEMCHECK_PRE_COLS)(*[int(x) if x else None for x in pre_ptrs]) if pre_ptrs is not None else None
+        dev = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.L.nx_trace_keccak_memory_check(self.ctx, dev(states_ptr), dev(addresses_ptr), dev(timestamps_ptr), C.c_uint32(int(n_instances)),
+                                                      C.c_uint32(int(log_size)), mp, pp, dev(states_out_ptr)))
 
     # ---- FriOps ----
     def fold_circle_into_line(self, tw, dst4, src4, alpha):

@@ -14,26 +14,11 @@ namespace nx {
 
 #include "trace_rows.h"
 #include "keccak_round.h"
+#include "keccak_store.h"
 
 static_assert(KR_MAIN_COLS == NX_KECCAK_ROUND_MAIN_COLS && KR_PRE_COLS == NX_KECCAK_ROUND_PRE_COLS, "keccak_round.h and nexus_hip.h disagree");
 
 constexpr u32 KR_THREADS = 256;
-#define NX_KR_CONSTANT __attribute__((address_space(4)))
-
-__device__ __forceinline__ u64 kr_gld64(const u64* p) { return *(NX_GLOBAL_AS const u64*)p; }
-__device__ __forceinline__ void kr_gst64(u64* p, u64 v) { *(NX_GLOBAL_AS u64*)p = v; }
-
-// cols: a table of column pointers in device memory; off: the byte offset of this lane's storage position (< 2^32: log_size <= 30)
-typedef u32* KrColumn;
-struct KrDevStore {
-    NX_KR_CONSTANT const KrColumn* cols; u32 off;
-    __device__ __forceinline__ void word(u32 col, u32 w) const { *(NX_GLOBAL_AS u32*)((NX_GLOBAL_AS char*)cols[col] + off) = w; }
-    __device__ __forceinline__ void put(u32 col, u64 lane) const {
-#pragma unroll
-        for (u32 b = 0; b < 8; b++) word(col + b, (u32)(lane >> (8 * b)) & 255u);
-    }
-};
-
 // table: KR_MAIN_COLS main column pointers, then (has_pre) KR_PRE_COLS preprocessed ones
 __global__ __launch_bounds__(KR_THREADS) void keccak_round_kernel(const u64* __restrict__ states, u32 n_instances, u32 first_round, u32 log_rounds, int log_size,
                                                                   u32* const* __restrict__ table, u32 has_pre, u64* __restrict__ states_out) {

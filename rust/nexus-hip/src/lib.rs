@@ -474,6 +474,22 @@ impl Session {
         try_check(self.ctx, sys::nx_trace_keccak_round(self.ctx, d_states, n_instances, first_round, log_rounds, log_size, main.as_ptr(),
                                                        if pre.is_empty() { std::ptr::null() } else { pre.as_ptr() }, d_states_out))
     }
+    /// The PermutationMemoryCheck component's trace filled on the device (`nx_trace_keccak_memory_check`): what the reference's
+    /// `generate_keccak_mem_check_trace` builds on the CPU with a full keccakf per row (prover/src/extensions/keccak/memory_check/
+    /// trace.rs:32-123).  `d_states`: `n_instances` x 25 lanes, `d_addresses`: `n_instances` words, `d_timestamps`: `n_instances` x 200
+    /// words, 16-byte aligned (null when there are none); natural row `r` is instance `r`.  `main`: the
+    /// `NX_KECCAK_MEMCHECK_MAIN_COLS` columns in the order of trace.rs:34, `pre`: empty or the one is_last column, `d_states_out`: null
+    /// or where keccak-f[1600] of the inputs goes.  `addr + i` and `ts + 1` are taken modulo 2^32.  Stream-ordered.
+    ///
+    /// # Safety
+    /// Every pointer must be valid device memory of the size the header states; columns must not alias.
+    pub unsafe fn trace_keccak_memory_check(&mut self, d_states: *const u64, d_addresses: *const u32, d_timestamps: *const u32, n_instances: u32, log_size: u32,
+                                            main: &[*mut u32], pre: &[*mut u32], d_states_out: *mut u64) -> Result<(), HipError> {
+        if main.len() != sys::NX_KECCAK_MEMCHECK_MAIN_COLS as usize { return Err(HipError::Argument("trace_keccak_memory_check: 2001 main columns".into())); }
+        if !pre.is_empty() && pre.len() != sys::NX_KECCAK_MEMCHECK_PRE_COLS as usize { return Err(HipError::Argument("trace_keccak_memory_check: no or 1 preprocessed column".into())); }
+        try_check(self.ctx, sys::nx_trace_keccak_memory_check(self.ctx, d_states, d_addresses, d_timestamps, n_instances, log_size, main.as_ptr(),
+                                                              if pre.is_empty() { std::ptr::null() } else { pre.as_ptr() }, d_states_out))
+    }
     /// Compiled AIR / fraction kernels are kept in `dir` across processes (`nx_air_cache_dir`): the first proof of a process loads
     /// them in milliseconds instead of paying hiprtc (seconds for an AIR of the reference's size).  Process-wide.
     pub fn kernel_cache_dir(dir: &str) -> Result<(), HipError> {
