@@ -241,7 +241,10 @@ int nx_accumulate_quotients(nx_ctx* ctx, uint32_t log_size, const uint32_t* cons
 /* Column-sharded variant: the quotient is a sum over columns, so each GPU accumulates the entries whose
  * columns it holds (entry_local[k] != 0; col_idx[k] then indexes ITS d_cols) with the alpha power of the entry's GLOBAL
  * position, exactly one GPU adds the line terms of all entries (include_line_terms), and the partial results are summed
- * mod p across GPUs (nx_comm.allreduce_m31).  Batches, counts, values describe ALL entries, on every GPU. */
+ * mod p across GPUs (nx_comm.allreduce_m31).  Batches, counts, values describe ALL entries, on every GPU.  col_idx of a non-local
+ * entry (entry_local[k] == 0) is ignored, whatever it holds (0xFFFFFFFF by convention); entry_local == NULL means every entry is
+ * local, and with include_line_terms the call is then nx_accumulate_quotients.  n_cols == 0 is allowed (a GPU that holds no column of
+ * this size group; d_cols may then be NULL): it still passes every entry, and writes the line terms or, without them, zeros. */
 int nx_accumulate_quotients_partial(nx_ctx* ctx, uint32_t log_size, const uint32_t* const* d_cols, uint32_t n_cols,
                                     const uint32_t random_coeff[4], uint32_t n_batches, const uint32_t* points,
                                     const uint32_t* batch_counts, const uint32_t* col_idx, const uint32_t* values,
@@ -276,7 +279,8 @@ int nx_fri_decompose(nx_ctx* ctx, const uint32_t* const* d_src4, uint32_t log_si
 
 /* --------------------------------------------------------------- K10: GrindOps ------------- */
 /* GrindOps<Blake2sChannel>::grind: smallest nonce with >= pow_bits trailing zero bits of
- * Blake2s(digest ‖ nonce_le64) read as a little-endian u128. */
+ * Blake2s(digest ‖ nonce_le64) read as a little-endian u128.  The search runs in launches of at most 2^24 nonces, the first one 64 x
+ * 2^pow_bits of them: from about 22 bits the smallest nonce often lies beyond the first launch and the search takes several. */
 int nx_grind(nx_ctx* ctx, const uint8_t digest[32], uint32_t pow_bits, uint64_t* nonce);
 
 /* ------------------------------------------- synthetic machine (BASELINE configs #2-#4) ---- */

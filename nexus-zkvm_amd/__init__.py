@@ -1139,6 +1139,25 @@ class HipBackend:
                                                  cidx.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p), out.col_ptrs()))
         return out
 
+    def accumulate_quotients_partial(self, cols, log_size, random_coeff, batches, entry_local, include_line_terms, out=None):
+        """nx_accumulate_quotients_partial, one rank's share of a column-sharded quotient: cols = the DeviceColumns this rank holds (None:
+        it holds none), batches as for accumulate_quotients but over ALL entries, a local entry's col_idx counted in `cols`, any other's
+        ignored; entry_local = one flag per flattened entry (None: all local).  Returns the 4-column partial sum (written into `out`)."""
+        out = DeviceColumns(self, 4, log_size) if out is None else out
+        pts = _u32([b[0] for b in batches]).reshape(-1)
+        counts = _u32([len(b[1]) for b in batches])
+        cidx = _u32([cv[0] for b in batches for cv in b[1]])
+        vals = _u32([cv[1] for b in batches for cv in b[1]]).reshape(-1)
+        a = _u32(random_coeff)
+        loc = None if entry_local is None else np.ascontiguousarray(entry_local, dtype=np.uint8)
+        self._chk(self.L.nx_accumulate_quotients_partial(self.ctx, log_size, cols.col_ptrs() if cols is not None else None,
+                                                         cols.n_cols if cols is not None else 0, a.ctypes.data_as(C.c_void_p),
+                                                         len(batches), pts.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                                         cidx.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p),
+                                                         loc.ctypes.data_as(C.c_void_p) if loc is not None else None, int(bool(include_line_terms)),
+                                                         out.col_ptrs()))
+        return out
+
     # ---- recorded AIR constraints (SURVEY §8(f) rank 1) ----
     def eval_constraint_program(self, program, column_ptrs, alpha_powers, denom_inv, log_size, log_eval, acc4):
         """Run an air_program.Program over every row of the evaluation domain and accumulate into acc4 (a 4-column

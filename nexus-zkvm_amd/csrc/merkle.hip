@@ -1210,7 +1210,8 @@ int nx_grind(nx_ctx* ctx, const uint8_t digest[32], uint32_t pow_bits, uint64_t*
     NX_TRY(dev_alloc(ctx, sizeof h, (void**)&d));
     hipError_t e = hipMemcpyAsync(d, &h, sizeof h, hipMemcpyHostToDevice, ctx->stream);
     // the first launch tries 64 x the expected number of nonces (2^pow_bits): enough with probability 1 - e^-64, ~10 us for the
-    // default 10 bits instead of the 108 us of a fixed 2^22 batch; later launches (never needed in practice) double up to 2^24
+    // default 10 bits instead of the 108 us of a fixed 2^22 batch; later launches double up to 2^24 (never needed up to 18 bits; from about
+    // 22 bits the first launch is capped at 2^24 nonces, no longer 64 x the expected count, and the search takes several)
     uint64_t batch = std::min<uint64_t>(1ull << 24, std::max<uint64_t>(1ull << 16, 64ull << std::min<uint32_t>(pow_bits, 18)));
     uint64_t base = 0;
     unsigned long long res = ~0ull;
