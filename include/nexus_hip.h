@@ -1025,6 +1025,66 @@ int nx_trace_keccak_memory_check(nx_ctx* ctx, const uint64_t* d_states, const ui
                                  uint32_t n_instances, uint32_t log_size, uint32_t* const* d_main, uint32_t* const* d_pre,
                                  uint64_t* d_states_out);
 
+/* ------------------------------------------- the step table split into per-opcode component traces on the device ------------------
+ * Every execution component of the reference's v2 prover takes the steps of its own opcode only: ExecutionComponent::iter_program_steps
+ * (prover2/machine/src/components/execution/common/mod.rs:31-39) filters the whole execution by OPCODE, row i of the component is the
+ * i-th such step, and the trace is padded to 2^max(ceil_log2(count), LOG_N_LANES) rows with IsLocalPad = 1 (execution/add/mod.rs:
+ * 157-183; the same in sub, sll, load, store ...); the Cpu component takes every step (components/cpu/trace.rs:36-59).  The four device
+ * fills above want a component's seed columns in device memory, one row per step OF THAT COMPONENT; these two calls make them from ONE
+ * step table, so an execution crosses PCIe once, as 32-bit words.
+ * STEP TABLE: n_src device columns of n_steps words in step order — linear, NOT bit-reversed; 0 <= n_steps <= 2^30 (pc, clk, instr,
+ * operand values, a result ...).  CLASS COLUMN d_class: n_steps words, the component of each step, 0 .. n_classes - 1, or NX_PART_NONE
+ * for a step that belongs to no component; 1 <= n_classes <= NX_PART_MAX_CLASSES.
+ * nx_trace_partition_create counts the steps of every class into counts[n_classes] (host memory; blocking, like the other calls that
+ * report a count) and keeps the STABLE ORDER — for class c the steps with d_class == c in execution order — in *out: one index array
+ * of n_steps words from the context's allocator, released by nx_trace_partition_destroy (NULL is fine), and n_classes + 1 offsets in
+ * host memory; nothing else stays on the device.  One 8-bit counting pass: per-block class histogram, scan, stable placement.  d_class
+ * is read again by no later call, but nx_trace_partition_fill compares its pointer with the outputs.
+ * nx_trace_partition_log_size(count, min_log) = max(ceil_log2(count), min_log), count 0 giving min_log: the component's log_size for
+ * nx_prover_tree_begin.  Pure host arithmetic.
+ * nx_trace_partition_fill makes n_dests components in one call.  A destination has a class (NX_PART_ALL: every step in step order,
+ * the Cpu component), a log_size in 1..30 with 2^log_size >= the class's count, n_cols output columns of 2^log_size words — TRACE-
+ * DOMAIN EVALUATIONS in bit-reversed circle-domain order, the rule of nx_trace_program — and one limb spec {src, shift, bits} per
+ * output column: natural row r < count holds (d_src[src][step_r] >> shift) & (2^bits - 1), step_r the r-th step of the class;
+ * 1 <= bits <= 31, shift + bits <= 32; the value p is written as 0 (nx_trace_program's rule for integer results).  Rows r >= count
+ * hold 0.  d_is_pad (optional): 0 on real rows, 1 on padding rows (IsLocalPad / IsPad); d_step (optional): the step index of the row,
+ * 0 on padding rows.  EVERY word of every output is written: no memset is needed.  The reference's fill_columns(row, pc_parts,
+ * Column::Pc) and fill_columns_bytes(row, &value_b, Column::BVal) become limb specs over one word column; derived columns (PcCarry,
+ * ClkCarry, AVal, HCarry ...) stay with nx_trace_program on the component's own columns.  Several destinations may have one class.  A
+ * source word is loaded once per row however many limbs are cut from it.  Stream-ordered like nx_trace_program; no device memory is
+ * allocated by the fill, the descriptor tables travel through the context's staging ring.
+ * Exact integers: the same words on every run.
+ * NX_ERR_ARG (nx_last_error names the argument; nothing is launched): a NULL ctx, out, counts or partition; d_class NULL with
+ * n_steps > 0; n_classes of 0 or above 256; n_steps above 2^30; a context that is not the partition's; a destination whose class is
+ * >= n_classes and not NX_PART_ALL; a log_size outside 1..30 or with 2^log_size < count; src >= n_src; bad shift / bits; a NULL
+ * output column, or a NULL d_src entry that a spec names when n_steps > 0; an output pointer (column, d_is_pad, d_step) equal to
+ * another output of the call or to a source or class column.
+ * NX_ERR_PROTOCOL (create): a class word >= n_classes that is not NX_PART_NONE; nx_last_error names the SMALLEST such step and its
+ * word, "step 17: class 300, 40 classes"; *out is NULL, the context stays usable and its live bytes are what they were.
+ * n_steps == 0 is valid: every count is 0, every destination row is padding.
+ * DEVICE MEMORY: create keeps 4 n_steps bytes (the order) and needs, until it returns, 4 n_classes B + 1280 bytes more, B <= 1024
+ * the blocks of the counting pass (each term rounded up to 256). */
+#define NX_PART_NONE 0xFFFFFFFFu       /* class word of a step that belongs to no component */
+#define NX_PART_ALL  0xFFFFFFFFu       /* class of a destination that takes every step in step order */
+#define NX_PART_MAX_CLASSES 256
+typedef struct nx_partition nx_partition;
+typedef struct nx_part_limb { uint32_t src, shift, bits; } nx_part_limb;
+typedef struct nx_part_dest {
+    uint32_t cls;                      /* 0 .. n_classes - 1, or NX_PART_ALL                                  */
+    uint32_t log_size;                 /* 1 .. 30, 2^log_size >= the steps of the class                       */
+    uint32_t n_cols;
+    uint32_t* const* d_cols;           /* n_cols output columns of 2^log_size words                           */
+    const nx_part_limb* limbs;         /* n_cols specs, one per output column                                 */
+    uint32_t* d_is_pad;                /* NULL, or output: 0 on real rows, 1 on padding rows                  */
+    uint32_t* d_step;                  /* NULL, or output: the step index of the row, 0 on padding rows       */
+} nx_part_dest;
+int nx_trace_partition_create(nx_ctx* ctx, const uint32_t* d_class, uint32_t n_steps, uint32_t n_classes, uint32_t* counts,
+                              nx_partition** out);
+uint32_t nx_trace_partition_log_size(uint64_t count, uint32_t min_log);
+int nx_trace_partition_fill(nx_ctx* ctx, const nx_partition* part, const uint32_t* const* d_src, uint32_t n_src,
+                            const nx_part_dest* dests, uint32_t n_dests);
+void nx_trace_partition_destroy(nx_partition* part);
+
 /* Config #2: LDE + Blake2s commit of n_cols random columns of 2^log_size rows (already resident,
  * bit-reversed evaluations, overwritten by their coefficients); d_lde receives the LDE columns. */
 int nx_lde_commit(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, uint32_t n_cols, uint32_t log_size,

@@ -642,6 +642,72 @@ class AccessSummary(C.Structure):
     _fields_ = [("cap", C.c_uint32), ("d_key", C.c_void_p), ("d_count", C.c_void_p), ("d_last", C.c_void_p)]
 
 
+class PartLimb(C.Structure):
+    """nx_part_limb of include/nexus_hip.h."""
+    _fields_ = [("src", C.c_uint32), ("shift", C.c_uint32), ("bits", C.c_uint32)]
+
+
+class PartDest(C.Structure):
+    """nx_part_dest of include/nexus_hip.h."""
+    _fields_ = [("cls", C.c_uint32), ("log_size", C.c_uint32), ("n_cols", C.c_uint32), ("d_cols", C.c_void_p), ("limbs", C.c_void_p), ("d_is_pad", C.c_void_p),
+                ("d_step", C.c_void_p)]
+
+
+PART_NONE = PART_ALL = 0xFFFFFFFF   # NX_PART_NONE (a class word), NX_PART_ALL (a destination's class)
+PART_MAX_CLASSES = 256              # NX_PART_MAX_CLASSES
+
+
+def partition_log_size(count, min_log):
+    """nx_trace_partition_log_size: max(ceil_log2(count), min_log), the log_size of a component with `count` steps.  Host only."""
+    L = load_library()
+    L.nx_trace_partition_log_size.restype = C.c_uint32
+    L.nx_trace_partition_log_size.argtypes = [C.c_uint64, C.c_uint32]
+    return int(L.nx_trace_partition_log_size(int(count), int(min_log)))
+
+
+class TracePartition:
+    """The stable order of a step table by class (nx_partition), from HipBackend.trace_partition.  counts: steps per class."""
+
+    def __init__(self, backend, handle, counts, n_steps):
+        self.be, self.h, self.counts, self.n_steps = backend, handle, counts, n_steps
+
+    def fill(self, src_ptrs, dests, want_rc=False):
+        """nx_trace_partition_fill: every destination (one component) from the step table in one call.  src_ptrs: device addresses of
+        the table's columns, n_steps words each in step order; dests: dicts with cls (a class, or PART_ALL for every step), log_size,
+        cols (device addresses of 2^log_size words, bit-reversed circle-domain order), limbs (one (src, shift, bits) per column: natural
+        row r holds (src[step_r] >> shift) & (2^bits - 1)), optional is_pad / step (output addresses).  Stream-ordered.  want_rc:
+        the return code instead of raising on NX_ERR_ARG."""
+        keep = []
+        arr = (PartDest * max(1, len(dests)))()
+        for i, d in enumerate(dests):
+            cols, limbs = list(d.get("cols", ())), list(d.get("limbs", ()))
+            if len(cols) != len(limbs):
+                raise NexusHipError(f"trace_partition fill: destination {i} has {len(cols)} columns and {len(limbs)} limb specs")
+            cp = (C.c_void_p * max(1, len(cols)))(*[int(x) if x else None for x in cols])
+            lp = (PartLimb * max(1, len(limbs)))(*[PartLimb(int(s), int(sh), int(b)) for s, sh, b in limbs])
+            keep += [cp, lp]
+            arr[i] = PartDest(int(d["cls"]), int(d["log_size"]), len(cols), C.cast(cp, C.c_void_p), C.cast(lp, C.c_void_p),
+                              int(d["is_pad"]) if d.get("is_pad") else None, int(d["step"]) if d.get("step") else None)
+        sp = (C.c_void_p * max(1, len(src_ptrs)))(*[int(x) if x else None for x in src_ptrs])
+        rc = self.be.L.nx_trace_partition_fill(self.be.ctx, self.h, sp, C.c_uint32(len(src_ptrs)), arr, C.c_uint32(len(dests)))
+        del keep
+        if want_rc and rc in (NX_OK, NX_ERR_ARG):
+            return rc
+        self.be._chk(rc)
+        return rc
+
+    def destroy(self):
+        if self.h and self.be.ctx:
+            self.be.L.nx_trace_partition_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
 MULT_LDS_MAX_KEY_BITS = 12   # NX_MULT_LDS_MAX_KEY_BITS: widest key space nx_logup_multiplicities counts in LDS
 KECCAK_ROUND_MAIN_COLS, KECCAK_ROUND_PRE_COLS = 1705, 9   # NX_KECCAK_ROUND_MAIN_COLS, NX_KECCAK_ROUND_PRE_COLS
 KECCAK_MEMCHECK_MAIN_COLS, KECCAK_MEMCHECK_PRE_COLS = 2001, 1   # NX_KECCAK_MEMCHECK_MAIN_COLS, NX_KECCAK_MEMCHECK_PRE_COLS
@@ -683,6 +749,8 @@ def load_library():
     L.nx_committed_tree_release.argtypes = [C.c_void_p]
     L.nx_committed_tree_release.restype = None
     L.nx_verifier_destroy.argtypes = [C.c_void_p]
+    L.nx_trace_partition_destroy.argtypes = [C.c_void_p]
+    L.nx_trace_partition_destroy.restype = None
     L.nx_verifier_destroy.restype = None
     L.nx_verifier_last_error.argtypes = [C.c_void_p]
     L.nx_verifier_last_error.restype = C.c_char_p
@@ -1418,6 +1486,23 @@ class HipBackend:
         dev = lambda p: C.c_void_p(int(p)) if p else None
         self._chk(self.L.nx_trace_keccak_memory_check(self.ctx, dev(states_ptr), dev(addresses_ptr), dev(timestamps_ptr), C.c_uint32(int(n_instances)),
                                                       C.c_uint32(int(log_size)), mp, pp, dev(states_out_ptr)))
+
+    def trace_partition(self, class_ptr, n_steps, n_classes, want_rc=False):
+        """nx_trace_partition_create: the steps of an execution split by class.  class_ptr: device address of n_steps words, the
+        component of every step (0 .. n_classes - 1, or PART_NONE: in no component).  Returns (counts, handle): the steps of every class
+        as a uint32 array, and a TracePartition whose fill(...) makes the components' columns and whose destroy() releases the order
+        (n_steps words of device memory).  Blocking.  Raises as the neighbours do, also on NX_ERR_PROTOCOL (a class word outside the
+        classes; the message names the smallest such step) unless want_rc: then (counts or None, handle or None, code)."""
+        counts = np.zeros(max(1, int(n_classes)), np.uint32)
+        h = C.c_void_p()
+        rc = self.L.nx_trace_partition_create(self.ctx, C.c_void_p(int(class_ptr)) if class_ptr else None, C.c_uint32(int(n_steps)), C.c_uint32(int(n_classes)),
+                                              counts.ctypes.data_as(C.c_void_p), C.byref(h))
+        if want_rc and rc in (NX_OK, NX_ERR_PROTOCOL, NX_ERR_ARG):
+            ok = rc == NX_OK
+            return (counts[:int(n_classes)] if ok else None), (TracePartition(self, h, counts[:int(n_classes)], int(n_steps)) if ok else None), rc
+        self._chk(rc)
+        counts = counts[:int(n_classes)]
+        return counts, TracePartition(self, h, counts, int(n_steps))
 
     # ---- FriOps ----
     def fold_circle_into_line(self, tw, dst4, src4, alpha):

@@ -490,6 +490,30 @@ impl Session {
         try_check(self.ctx, sys::nx_trace_keccak_memory_check(self.ctx, d_states, d_addresses, d_timestamps, n_instances, log_size, main.as_ptr(),
                                                               if pre.is_empty() { std::ptr::null() } else { pre.as_ptr() }, d_states_out))
     }
+    /// The steps of an execution split by component (`nx_trace_partition_create`): what every v2 execution component does on the CPU
+    /// with `ExecutionComponent::iter_program_steps` (prover2/machine/src/components/execution/common/mod.rs:31-39).  `d_class`:
+    /// `n_steps` words in device memory, the component of each step (`0 .. n_classes - 1`, or `PART_NONE`).  Returns the steps of every
+    /// class and the handle that keeps their stable order (`n_steps` words of device memory) until it is dropped.  A class word outside
+    /// the classes is `HipError` from NX_ERR_PROTOCOL, naming the smallest such step.  Blocking.
+    ///
+    /// # Safety
+    /// `d_class` must be valid device memory of `n_steps` words and outlive the handle's fills.
+    pub unsafe fn trace_partition(&mut self, d_class: *const u32, n_steps: u32, n_classes: u32) -> Result<(Vec<u32>, TracePartition), HipError> {
+        let mut counts = vec![0u32; n_classes.max(1) as usize];
+        let mut h: *mut sys::nx_partition = std::ptr::null_mut();
+        try_check(self.ctx, sys::nx_trace_partition_create(self.ctx, d_class, n_steps, n_classes, counts.as_mut_ptr(), &mut h))?;
+        counts.truncate(n_classes as usize);
+        Ok((counts, TracePartition { ctx: self.ctx, h }))
+    }
+    /// Every component of `dests` from the step table in one launch (`nx_trace_partition_fill`): the `generate_main_trace` loops of the
+    /// v2 components (execution/add/mod.rs:157-183) with `fill_columns` / `fill_columns_bytes` as limb specs over the table's word
+    /// columns.  `log_size` of a destination: `partition_log_size(count, LOG_N_LANES)`.  Stream-ordered.
+    ///
+    /// # Safety
+    /// Every pointer inside `d_src` and `dests` must be valid device memory of the size the header states; outputs must not alias.
+    pub unsafe fn trace_partition_fill(&mut self, part: &TracePartition, d_src: &[*const u32], dests: &[sys::nx_part_dest]) -> Result<(), HipError> {
+        try_check(self.ctx, sys::nx_trace_partition_fill(self.ctx, part.h, d_src.as_ptr(), d_src.len() as u32, dests.as_ptr(), dests.len() as u32))
+    }
     /// Compiled AIR / fraction kernels are kept in `dir` across processes (`nx_air_cache_dir`): the first proof of a process loads
     /// them in milliseconds instead of paying hiprtc (seconds for an AIR of the reference's size).  Process-wide.
     pub fn kernel_cache_dir(dir: &str) -> Result<(), HipError> {
@@ -581,6 +605,16 @@ impl Verifier {
     }
 }
 impl Drop for Verifier { fn drop(&mut self) { unsafe { sys::nx_verifier_destroy(self.v) } } }
+
+/// The stable order of a step table by component (`nx_partition`), from `Session::trace_partition`; releases its `n_steps` words of
+/// device memory when dropped.  Must not outlive the session whose context made it.
+pub struct TracePartition { #[allow(dead_code)] ctx: *mut sys::nx_ctx, h: *mut sys::nx_partition }
+impl Drop for TracePartition { fn drop(&mut self) { unsafe { sys::nx_trace_partition_destroy(self.h) } } }
+/// `NX_PART_NONE`: the class word of a step that belongs to no component; `NX_PART_ALL`: the class of a destination that takes every step.
+pub const PART_NONE: u32 = 0xFFFF_FFFF;
+pub const PART_ALL: u32 = 0xFFFF_FFFF;
+/// `num.next_power_of_two().ilog2().max(LOG_N_LANES)` of the v2 components' `generate_main_trace` (`nx_trace_partition_log_size`).
+pub fn partition_log_size(count: u64, min_log: u32) -> u32 { unsafe { sys::nx_trace_partition_log_size(count, min_log) } }
 
 /// `nexus_vm_prover::verify` (machine.rs:363-500; prover2 verify.rs:28-160) of the NXP1 words a `Session::prove` returned, for a
 /// statement of the reference's shape — three trace trees, claimed sums mixed before the interaction tree: `prefix` is what the prover
