@@ -190,7 +190,22 @@ __device__ __forceinline__ uint32_t gld_off(const uint32_t* base, uint32_t byte_
 __device__ __forceinline__ uint4 gld4(const uint32_t* p) { const nx_v4u32 v = *(NX_GLOBAL_AS const nx_v4u32*)p; return make_uint4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ void gst(uint32_t* p, uint32_t v) { *(NX_GLOBAL_AS uint32_t*)p = v; }
 __device__ __forceinline__ void gst4(uint32_t* p, uint4 v) { nx_v4u32 w = {v.x, v.y, v.z, v.w}; *(NX_GLOBAL_AS nx_v4u32*)p = w; }
+// 4 consecutive rows of one column of n rows: one 16-byte load where the caller knows the quad whole and aligned (vec), guarded words
+// elsewhere (rows past n read as 0)
+__device__ __forceinline__ uint4 gld4_guarded(const uint32_t* col, uint32_t row, uint32_t n, bool vec) {
+    if (vec) return gld4(col + row);
+    uint4 r = make_uint4(0, 0, 0, 0);
+    if (row < n) r.x = gld(col + row);
+    if (row + 1 < n) r.y = gld(col + row + 1);
+    if (row + 2 < n) r.z = gld(col + row + 2);
+    if (row + 3 < n) r.w = gld(col + row + 3);
+    return r;
+}
 #endif
+
+// A key packed from up to 4 column entries: entry c takes bits[c] bits at shift[c] (nx_logup_multiplicities, nx_trace_prev_access; each
+// validates its own limits)
+struct PackedKey { uint32_t n_cols, bits[4], shift[4], total_bits; };
 
 // Row-sharded proves (one contiguous block of the bit-reversed rows per GPU): kernels index every column with the GLOBAL row, the
 // host hands them the block pointer moved back by the block's first row.  Only addresses p[row_begin ...] are ever dereferenced.

@@ -30,7 +30,6 @@ constexpr u64 MULT_TAKEN = ~(u64)0;            // a counter the scatter pass has
 constexpr u32 MULT_MAX_USES = 1u << 16;
 
 struct MultUse { const u32* col[4]; const u32* weight; u32 log_size, vec; };
-struct MultKey { u32 n_cols, bits[4], shift[4], total_bits; };
 // results and flags of one call, one 64-byte block of device memory
 struct MultCtl {
     u64 residual;        // weight counted on keys no table row has
@@ -48,21 +47,10 @@ __device__ __forceinline__ u64 wave_sum(u64 v) {
     return v;
 }
 
-// 4 consecutive rows of one column: one 16-byte load inside a full, aligned tile, guarded words elsewhere (rows past n read as 0)
-__device__ __forceinline__ uint4 mult_ld4(const u32* col, u32 row, u32 n, bool vec) {
-    if (vec) return gld4(col + row);
-    uint4 r = make_uint4(0, 0, 0, 0);
-    if (row < n) r.x = gld(col + row);
-    if (row + 1 < n) r.y = gld(col + row + 1);
-    if (row + 2 < n) r.z = gld(col + row + 2);
-    if (row + 3 < n) r.w = gld(col + row + 3);
-    return r;
-}
-
 // The 16 rows of this lane in the tile at `row0` of use `u`: row (q, e) is row0 + (q * 256 + lane) * 4 + e.  key: the packed key;
 // wt: the numerator (1 without a weight column), 0 for a row past the end, a weight-0 row and — with its bit set in *bad — a row
 // that has a nonzero weight and an entry outside its key_bits.
-__device__ __forceinline__ void mult_load_tile(const MultUse& u, const MultKey& K, u32 row0, u32 key[16], u32 wt[16], u32* bad) {
+__device__ __forceinline__ void mult_load_tile(const MultUse& u, const PackedKey& K, u32 row0, u32 key[16], u32 wt[16], u32* bad) {
     const u32 n = 1u << u.log_size;
     const bool vec = u.vec != 0;
     uint4 v[4][MULT_QUADS], w[MULT_QUADS];
@@ -70,12 +58,12 @@ __device__ __forceinline__ void mult_load_tile(const MultUse& u, const MultKey& 
     for (u32 c = 0; c < 4; c++)
         if (c < K.n_cols) {
 #pragma unroll
-            for (u32 q = 0; q < MULT_QUADS; q++) v[c][q] = mult_ld4(u.col[c], row0 + (q * MULT_THREADS + threadIdx.x) * 4, n, vec);
+            for (u32 q = 0; q < MULT_QUADS; q++) v[c][q] = gld4_guarded(u.col[c], row0 + (q * MULT_THREADS + threadIdx.x) * 4, n, vec);
         }
 #pragma unroll
     for (u32 q = 0; q < MULT_QUADS; q++) {
         const u32 r = row0 + (q * MULT_THREADS + threadIdx.x) * 4;
-        if (u.weight) w[q] = mult_ld4(u.weight, r, n, vec);
+        if (u.weight) w[q] = gld4_guarded(u.weight, r, n, vec);
         else w[q] = make_uint4(r < n, r + 1 < n, r + 2 < n, r + 3 < n);
     }
     u32 b = 0;
@@ -125,7 +113,7 @@ struct MultWalk {
 
 // LDS: block-private counters, flushed at the end.  !LDS: every add goes to the global counters.
 template <bool LDS>
-__global__ __launch_bounds__(MULT_THREADS) void mult_count_kernel(const MultUse* __restrict__ uses, const u32* __restrict__ tile_start, u32 n_uses, MultKey K,
+__global__ __launch_bounds__(MULT_THREADS) void mult_count_kernel(const MultUse* __restrict__ uses, const u32* __restrict__ tile_start, u32 n_uses, PackedKey K,
                                                                   u64* __restrict__ counters, MultCtl* __restrict__ ctl) {
     __shared__ u64 lds[LDS ? MULT_LDS_WORDS : 1];
     const u32 n_keys = 1u << K.total_bits;
@@ -182,7 +170,7 @@ __global__ __launch_bounds__(MULT_THREADS) void mult_count_kernel(const MultUse*
     }
 }
 
-__global__ __launch_bounds__(256) void mult_scatter_kernel(ColSet table, MultKey K, u32 n_rows, u64* __restrict__ counters, u32* __restrict__ d_mult, MultCtl* __restrict__ ctl) {
+__global__ __launch_bounds__(256) void mult_scatter_kernel(ColSet table, PackedKey K, u32 n_rows, u64* __restrict__ counters, u32* __restrict__ d_mult, MultCtl* __restrict__ ctl) {
     const u32 pos = blockIdx.x * blockDim.x + threadIdx.x;
     if (pos >= n_rows) return;
     u32 key = 0, out = 0;
@@ -201,7 +189,7 @@ __global__ __launch_bounds__(256) void mult_residual_kernel(const u64* __restric
 }
 
 // after the scatter pass: a counted row is missing when its key's counter was not taken
-__global__ __launch_bounds__(MULT_THREADS) void mult_missing_kernel(const MultUse* __restrict__ uses, const u32* __restrict__ tile_start, u32 n_uses, MultKey K,
+__global__ __launch_bounds__(MULT_THREADS) void mult_missing_kernel(const MultUse* __restrict__ uses, const u32* __restrict__ tile_start, u32 n_uses, PackedKey K,
                                                                     const u64* __restrict__ counters, MultCtl* __restrict__ ctl) {
     MultWalk walk; walk.begin(uses, tile_start, n_uses);
     MultUse u; u32 row0;
@@ -235,7 +223,7 @@ int nx_logup_multiplicities(nx_ctx* ctx, const nx_lookup_use* uses, uint32_t n_u
     const char* who = "nx_logup_multiplicities";
     if (!ctx || !key_bits || !d_table || !d_mult || (n_uses && !uses)) return set_err(ctx, NX_ERR_ARG, std::string(who) + ": NULL argument");
     if (n_key_cols < 1 || n_key_cols > 4) return set_err(ctx, NX_ERR_ARG, std::string(who) + ": 1 to 4 key columns");
-    MultKey K; memset(&K, 0, sizeof K);
+    PackedKey K; memset(&K, 0, sizeof K);
     K.n_cols = n_key_cols;
     for (u32 c = 0; c < n_key_cols; c++) {
         if (key_bits[c] < 1 || key_bits[c] > 24) return set_err(ctx, NX_ERR_ARG, std::string(who) + ": key_bits of 1 to 24 per column");

@@ -7,11 +7,8 @@
 //              handle (first element of the stream + storage position); a row that does not access, or holds an entry outside its
 //              key_bits (recorded: min (stream << 32 | position)), gets the handle PA_NONE, which the last sort pass puts behind
 //              every key.  The zeros of the rows that do not access are written here.
-//   sort       stable LSD radix sort of the (key, handle) pairs, 8-bit digits, three launches per pass: per-block digit histogram,
-//              exclusive scan of the [digit][block] counts (one block), stable scatter.  Inside a block a wave ranks its 64
-//              elements with 8 ballots (the mask of the lanes that hold my digit; rank = its popcount below my lane), so equal
-//              digits — byte-limb traces have whole-zero columns — are combined before they meet an LDS counter: one lane per
-//              distinct digit and wave touches LDS, and the scatter uses plain LDS stores, no atomic at all.
+//   sort       stable LSD radix sort of the (key, handle) pairs, 8-bit digits: every pass is the counting pass of count_pass.cuh
+//              (histogram, scan, stable placement) with the policy PaSort, which takes the digit from the key and moves the pair.
 //   resolve    in sorted order element j continues the run of j - 1 or heads a new one: heads are counted and the last head is
 //              found per block, both scanned over the blocks (one block), then every element gathers the payload of j - 1 (or
 //              init), writes it with its ordinal j - head to its own storage position; heads and tails write the summary entry of
@@ -26,9 +23,9 @@
 namespace nx {
 
 #include "trace_rows.h"
+#include "count_pass.cuh"
 
-constexpr u32 PA_THREADS = 256, PA_ENUM_TILE = PA_THREADS * 4, PA_RES_TILE = PA_THREADS * 4;
-constexpr u32 PA_MIN_STEPS = 4, PA_MAX_SORT_BLOCKS = 1024;        // a sort block takes steps * 256 consecutive elements
+constexpr u32 PA_THREADS = CP_THREADS, PA_ENUM_TILE = PA_THREADS * 4, PA_RES_TILE = PA_THREADS * 4;
 constexpr u32 PA_NONE = 0xFFFFFFFFu;                             // handle of an element that is no access (handles are < 2^31)
 constexpr u32 PA_MAX_STREAMS = 1u << 16, PA_MAX_PAYLOAD = 16;
 
@@ -39,7 +36,6 @@ struct PaStream {
 };
 // streams of one epoch: ge[b] of them have >= 2^b rows, the others have small[b] rows together; base: first time index of the epoch
 struct PaEpoch { u32 base, ge[32], small[32]; };
-struct PaKey { u32 n_cols, bits[4], shift[4], total_bits; };
 struct PaPass { u32 shift, last, sentinel; };                    // digit = (key >> shift) & 255; in the last pass PA_NONE -> sentinel
 struct PaInit { u32 w[PA_MAX_PAYLOAD]; };
 struct PaSum { u32 cap; u32* key; u32* count; u32* last[PA_MAX_PAYLOAD]; };
@@ -47,29 +43,12 @@ struct PaCtl { u64 first_bad; u32 n_keys; u32 pad[13]; };       // one 64-byte b
 
 __device__ __forceinline__ u32 pa_bitlen(u32 x) { return x ? 32u - (u32)__builtin_clz(x) : 0u; }
 
-__device__ __forceinline__ uint4 pa_ld4(const u32* col, u32 row, u32 n, bool vec) {
-    if (vec) return gld4(col + row);
-    uint4 r = make_uint4(0, 0, 0, 0);
-    if (row < n) r.x = gld(col + row);
-    if (row + 1 < n) r.y = gld(col + row + 1);
-    if (row + 2 < n) r.z = gld(col + row + 2);
-    if (row + 3 < n) r.w = gld(col + row + 3);
-    return r;
-}
-
-// last index i < n with a[i] <= x (a ascending, a[0] <= x)
-__device__ __forceinline__ u32 pa_find(const u32* __restrict__ a, u32 n, u32 x) {
-    u32 lo = 0, hi = n;
-    while (hi - lo > 1) { const u32 mid = (lo + hi) / 2; if (a[mid] <= x) lo = mid; else hi = mid; }
-    return lo;
-}
-
 // One block per tile of 1024 storage positions of one stream (tile_start: first tile of every stream), four consecutive positions
 // per lane.
 __global__ __launch_bounds__(PA_THREADS) void pa_enumerate_kernel(const PaStream* __restrict__ streams, const PaEpoch* __restrict__ epochs, const u32* __restrict__ tile_start,
-                                                                  const u32* __restrict__ sbase, u32 n_streams, PaKey K, u32 n_payload, u32* const* __restrict__ prv,
+                                                                  const u32* __restrict__ sbase, u32 n_streams, PackedKey K, u32 n_payload, u32* const* __restrict__ prv,
                                                                   u32* __restrict__ keys, u32* __restrict__ vals, PaCtl* __restrict__ ctl) {
-    const u32 s = pa_find(tile_start, n_streams, blockIdx.x);
+    const u32 s = find_le(tile_start, n_streams, blockIdx.x);
     const PaStream& S = streams[s];                 // read where it is: a per-lane copy would put before_ge, indexed at run time, into scratch
     const PaEpoch* __restrict__ E = epochs + S.epoch_slot;
     const u32 n = 1u << S.log_size;
@@ -80,13 +59,13 @@ __global__ __launch_bounds__(PA_THREADS) void pa_enumerate_kernel(const PaStream
 #pragma unroll
     for (u32 c = 0; c < 4; c++)
         if (c < K.n_cols) {
-            const uint4 v = pa_ld4(S.key[c], row0, n, vec);
+            const uint4 v = gld4_guarded(S.key[c], row0, n, vec);
             const u32 x[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (u32 e = 0; e < 4; e++) { k[e] |= x[e] << K.shift[c]; o[e] |= K.bits[c] < 32 ? x[e] >> K.bits[c] : 0u; }
         }
     uint4 fv = make_uint4(1, 1, 1, 1);
-    if (S.flag) fv = pa_ld4(S.flag, row0, n, vec);
+    if (S.flag) fv = gld4_guarded(S.flag, row0, n, vec);
     const u32 f[4] = {fv.x, fv.y, fv.z, fv.w};
     const u32 base = gld(sbase + s), ebase = E->base;
 #pragma unroll
@@ -123,118 +102,30 @@ __device__ __forceinline__ u32 pa_digit(u32 key, u32 val, PaPass ps) {
     return (ps.last && val == PA_NONE) ? ps.sentinel : d;
 }
 
-// the lanes of this wave that hold digit d (lanes without an element hold none and are in no mask)
-__device__ __forceinline__ u64 pa_match(u32 d, bool have) {
-    u64 m = __ballot(have);
-#pragma unroll
-    for (u32 b = 0; b < 8; b++) {
-        const bool bit = (d >> b) & 1;
-        const u64 bb = __ballot(bit);
-        m &= bit ? bb : ~bb;
-    }
-    return m;
-}
-
-// hist[digit * blocks + block]: elements of the block's tile with that digit
-__global__ __launch_bounds__(PA_THREADS) void pa_hist_kernel(const u32* __restrict__ keys, const u32* __restrict__ vals, u32 total, u32 steps, PaPass ps, u32* __restrict__ hist) {
-    __shared__ u32 h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const u32 lane = threadIdx.x & 63;
-    for (u32 st = 0; st < steps; st++) {
-        const u32 j = (blockIdx.x * steps + st) * PA_THREADS + threadIdx.x;
+// one pass of the sort as a counting pass: the histogram needs the handle in the last pass only, the placement moves the pair
+struct PaSort {
+    const u32* kin; const u32* vin; u32* kout; u32* vout; PaPass ps;
+    struct Item { u32 key, val; };
+    __device__ __forceinline__ bool digit(u32 j, u32 total, u32* d) const {
         const bool have = j < total;
-        const u32 key = have ? gld(keys + j) : 0u, val = (have && ps.last) ? gld(vals + j) : 0u;
-        const u32 d = have ? pa_digit(key, val, ps) : 0u;
-        const u64 m = pa_match(d, have);
-        if (have && !(m & (((u64)1 << lane) - 1))) atomicAdd(&h[d], (u32)__popcll(m));     // the lowest lane of every digit of the wave
+        const u32 key = have ? gld(kin + j) : 0u, val = (have && ps.last) ? gld(vin + j) : 0u;
+        *d = have ? pa_digit(key, val, ps) : 0u;
+        return have;
     }
-    __syncthreads();
-    hist[threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
-}
-
-template <int OP> __device__ __forceinline__ u32 pa_op(u32 a, u32 b) { return OP ? (a > b ? a : b) : a + b; }   // 0: sum, 1: maximum; 0 is neutral for both
-
-// exclusive scan of one value per thread over the block's 256 threads, *total: over the whole block.  lds: 4 words, free again on return.
-template <int OP> __device__ __forceinline__ u32 pa_block_scan(u32 v, u32* lds, u32* total) {
-    const u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    u32 inc = v;
-#pragma unroll
-    for (u32 off = 1; off < 64; off <<= 1) {
-        const u32 t = __shfl(inc, (int)((lane - off) & 63), 64);
-        if (lane >= off) inc = pa_op<OP>(inc, t);
-    }
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    u32 base = 0, tot = 0;
-#pragma unroll
-    for (u32 i = 0; i < 4; i++) { const u32 x = lds[i]; if (i < w) base = pa_op<OP>(base, x); tot = pa_op<OP>(tot, x); }
-    __syncthreads();
-    const u32 prev = __shfl(inc, (int)((lane - 1) & 63), 64);
-    *total = tot;
-    return lane ? pa_op<OP>(base, prev) : base;
-}
-
-// in-place exclusive scan of a[0 .. n) by ONE block (a is 16-byte aligned); *total_out (optional): the scan over everything
-template <int OP> __global__ __launch_bounds__(PA_THREADS) void pa_scan_kernel(u32* __restrict__ a, u32 n, u32* __restrict__ total_out) {
-    __shared__ u32 lds[4];
-    u32 carry = 0;
-    for (u32 base = 0; base < n; base += PA_THREADS * 4) {
-        const u32 i = base + threadIdx.x * 4;
-        const uint4 v = pa_ld4(a, i, n, i + 3 < n);
-        const u32 x0 = v.x, x1 = pa_op<OP>(x0, v.y), x2 = pa_op<OP>(x1, v.z), x3 = pa_op<OP>(x2, v.w);
-        u32 tot;
-        const u32 run = pa_op<OP>(carry, pa_block_scan<OP>(x3, lds, &tot));
-        const uint4 out = make_uint4(run, pa_op<OP>(run, x0), pa_op<OP>(run, x1), pa_op<OP>(run, x2));
-        if (i + 3 < n) gst4(a + i, out);
-        else {
-            if (i < n) gst(a + i, out.x);
-            if (i + 1 < n) gst(a + i + 1, out.y);
-            if (i + 2 < n) gst(a + i + 2, out.z);
-        }
-        carry = pa_op<OP>(carry, tot);
-    }
-    if (threadIdx.x == 0 && total_out) *total_out = carry;
-}
-
-// offs: the scanned histogram.  Elements leave in the order they came in: by step, by wave, by lane.
-__global__ __launch_bounds__(PA_THREADS) void pa_scatter_kernel(const u32* __restrict__ kin, const u32* __restrict__ vin, u32* __restrict__ kout, u32* __restrict__ vout,
-                                                                u32 total, u32 steps, PaPass ps, const u32* __restrict__ offs) {
-    __shared__ u32 run[256];            // next free output slot of every digit
-    __shared__ u32 wc[2][4][256];       // per step parity and wave: elements with the digit (zero outside the step that fills it)
-    run[threadIdx.x] = offs[threadIdx.x * gridDim.x + blockIdx.x];
-    for (u32 i = 0; i < 8; i++) (&wc[0][0][0])[i * 256 + threadIdx.x] = 0;
-    __syncthreads();
-    const u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (u32 st = 0; st < steps; st++) {
-        const u32 par = st & 1;
-        const u32 j = (blockIdx.x * steps + st) * PA_THREADS + threadIdx.x;
+    __device__ __forceinline__ bool load(u32 j, u32 total, Item* it, u32* d) const {
         const bool have = j < total;
-        const u32 key = have ? gld(kin + j) : 0u, val = have ? gld(vin + j) : 0u;
-        const u32 d = have ? pa_digit(key, val, ps) : 0u;
-        const u64 m = pa_match(d, have);
-        const u32 rank = (u32)__popcll(m & (((u64)1 << lane) - 1));
-        if (have && rank == 0) wc[par][w][d] = (u32)__popcll(m);
-        __syncthreads();
-        if (have) {
-            u32 o = run[d] + rank;
-            for (u32 i = 0; i < w; i++) o += wc[par][i][d];
-            gst(kout + o, key); gst(vout + o, val);
-        }
-        __syncthreads();
-        const u32 s = wc[par][0][threadIdx.x] + wc[par][1][threadIdx.x] + wc[par][2][threadIdx.x] + wc[par][3][threadIdx.x];
-        if (s) {   // thread t owns digit t; these words are next written two steps on, next read after the coming barrier
-            run[threadIdx.x] += s;
-            wc[par][0][threadIdx.x] = 0; wc[par][1][threadIdx.x] = 0; wc[par][2][threadIdx.x] = 0; wc[par][3][threadIdx.x] = 0;
-        }
+        it->key = have ? gld(kin + j) : 0u; it->val = have ? gld(vin + j) : 0u;
+        *d = have ? pa_digit(it->key, it->val, ps) : 0u;
+        return have;
     }
-}
+    __device__ __forceinline__ void store(u32 slot, const Item& it) const { gst(kout + slot, it.key); gst(vout + slot, it.val); }
+};
 
 // the four sorted elements j0 .. j0 + 3 of a lane with their neighbours: is[e] heads a run, tail[e] ends one
 struct PaQuad { u32 key[4], val[4], prev_val; bool head[4], tail[4]; };
 __device__ __forceinline__ void pa_load_quad(const u32* __restrict__ keys, const u32* __restrict__ vals, u32 total, u32 j0, bool want_tail, PaQuad* q) {
     const bool full = j0 + 3 < total;
-    const uint4 kv = pa_ld4(keys, j0, total, full), vv = pa_ld4(vals, j0, total, full);
+    const uint4 kv = gld4_guarded(keys, j0, total, full), vv = gld4_guarded(vals, j0, total, full);
     q->key[0] = kv.x; q->key[1] = kv.y; q->key[2] = kv.z; q->key[3] = kv.w;
     q->val[0] = vv.x; q->val[1] = vv.y; q->val[2] = vv.z; q->val[3] = vv.w;
     u32 pk = 0, pv = PA_NONE;                                 // the element before: a PA_NONE neighbour never continues a run
@@ -261,8 +152,8 @@ __global__ __launch_bounds__(PA_THREADS) void pa_heads_kernel(const u32* __restr
 #pragma unroll
     for (u32 e = 0; e < 4; e++) if (q.head[e]) { cnt++; last = j0 + e + 1; }
     u32 tc, tl;
-    (void)pa_block_scan<0>(cnt, lds, &tc);
-    (void)pa_block_scan<1>(last, lds, &tl);
+    (void)block_scan<0>(cnt, lds, &tc);
+    (void)block_scan<1>(last, lds, &tl);
     if (threadIdx.x == 0) { blk_cnt[blockIdx.x] = tc; blk_last[blockIdx.x] = tl; }
 }
 
@@ -278,20 +169,20 @@ __global__ __launch_bounds__(PA_THREADS) void pa_resolve_kernel(const u32* __res
 #pragma unroll
     for (u32 e = 0; e < 4; e++) if (q.head[e]) { cnt++; last = j0 + e + 1; }
     u32 unused;
-    u32 seg = blk_cnt[blockIdx.x] + pa_block_scan<0>(cnt, lds, &unused);              // heads before this lane's elements
-    u32 start = pa_op<1>(blk_last[blockIdx.x], pa_block_scan<1>(last, lds, &unused)); // (index + 1) of the last head before them
+    u32 seg = blk_cnt[blockIdx.x] + block_scan<0>(cnt, lds, &unused);              // heads before this lane's elements
+    u32 start = scan_op<1>(blk_last[blockIdx.x], block_scan<1>(last, lds, &unused)); // (index + 1) of the last head before them
     for (u32 e = 0; e < 4; e++) {
         const u32 j = j0 + e;
         // The rows that do not access are sorted last, so nothing follows the first PA_NONE.  One exception: a call without any d_flag
         // and with whole-byte keys has PA_NONE only on REFUSED rows, which share digit 255 with real keys; the call then returns
-        // NX_ERR_PROTOCOL and its outputs are unspecified, and skipping the rest of the quad stays in bounds (pa_find never sees PA_NONE).
+        // NX_ERR_PROTOCOL and its outputs are unspecified, and skipping the rest of the quad stays in bounds (find_le never sees PA_NONE).
         if (j >= total || q.val[e] == PA_NONE) break;
         if (q.head[e]) { seg++; start = j + 1; }
         const u32 run = seg - 1, ordinal = j + 1 - start;
-        const u32 s = pa_find(sbase, n_streams, q.val[e]), pos = q.val[e] - sbase[s];
+        const u32 s = find_le(sbase, n_streams, q.val[e]), pos = q.val[e] - sbase[s];
         const u32 pval = e ? q.val[e - 1] : q.prev_val;
         u32 ps = 0, ppos = 0;
-        if (!q.head[e]) { ps = pa_find(sbase, n_streams, pval); ppos = pval - sbase[ps]; }
+        if (!q.head[e]) { ps = find_le(sbase, n_streams, pval); ppos = pval - sbase[ps]; }
         u32* ord = streams[s].ord;
         if (ord) gst(ord + pos, ordinal);
         const bool to_sum = q.tail[e] && run < sum.cap;
@@ -325,7 +216,7 @@ int nx_trace_prev_access(nx_ctx* ctx, const nx_access_stream* streams, uint32_t 
     if (n_streams < 1 || n_streams > PA_MAX_STREAMS) return set_err(ctx, NX_ERR_ARG, who + ": n_streams of " + std::to_string(n_streams) + ", 1 to 65536");
     if (n_key_cols < 1 || n_key_cols > 4) return set_err(ctx, NX_ERR_ARG, who + ": n_key_cols of " + std::to_string(n_key_cols) + ", 1 to 4");
     if (n_payload < 1 || n_payload > PA_MAX_PAYLOAD) return set_err(ctx, NX_ERR_ARG, who + ": n_payload of " + std::to_string(n_payload) + ", 1 to 16");
-    PaKey K; memset(&K, 0, sizeof K);
+    PackedKey K; memset(&K, 0, sizeof K);
     K.n_cols = n_key_cols;
     for (u32 c = 0; c < n_key_cols; c++) {
         if (key_bits[c] < 1 || key_bits[c] > 32) return set_err(ctx, NX_ERR_ARG, who + ": key_bits[" + std::to_string(c) + "] of " + std::to_string(key_bits[c]) + ", 1 to 32");
@@ -414,14 +305,13 @@ int nx_trace_prev_access(nx_ctx* ctx, const nx_access_stream* streams, uint32_t 
         ebase += e.small[31] + (cnt_log[g][31] << 31);            // every stream has fewer than 2^31 rows
     }
     const u32 total = (u32)rows;
-    const u32 steps = std::max<u32>(PA_MIN_STEPS, (u32)((rows + (u64)PA_THREADS * PA_MAX_SORT_BLOCKS - 1) / ((u64)PA_THREADS * PA_MAX_SORT_BLOCKS)));
-    const u32 sort_blocks = (u32)((rows + (u64)steps * PA_THREADS - 1) / ((u64)steps * PA_THREADS));
+    const CountPlan plan = count_plan(rows);
     const u32 res_blocks = (total + PA_RES_TILE - 1) / PA_RES_TILE;
     const u32 n_pass = any_flag ? K.total_bits / 8 + 1 : (K.total_bits + 7) / 8;
 
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t b_ctl = al(sizeof(PaCtl)), b_st = al(h_st.size() * sizeof(PaStream)), b_ep = al(h_ep.size() * sizeof(PaEpoch)), b_tile = al(h_tile.size() * 4),
-                 b_base = al(h_base.size() * 4), b_ptr = al(h_pay.size() * sizeof(void*)), b_elems = al((size_t)total * 4), b_hist = al((size_t)sort_blocks * 256 * 4),
+                 b_base = al(h_base.size() * 4), b_ptr = al(h_pay.size() * sizeof(void*)), b_elems = al((size_t)total * 4), b_hist = al((size_t)plan.blocks * 256 * 4),
                  b_blk = al((size_t)res_blocks * 4);
     uint8_t* blob = nullptr;
     NX_TRY(dev_alloc(ctx, b_ctl + b_st + b_ep + b_tile + b_base + 2 * b_ptr + 4 * b_elems + b_hist + 2 * b_blk, (void**)&blob));
@@ -451,17 +341,14 @@ int nx_trace_prev_access(nx_ctx* ctx, const nx_access_stream* streams, uint32_t 
     for (u32 p = 0; p < n_pass && e == hipSuccess; p++) {
         PaPass ps; ps.shift = 8 * p; ps.last = p + 1 == n_pass; ps.sentinel = std::min<u32>(255u, 1u << (K.total_bits - 8 * (n_pass - 1)));
         // (255 only without any d_flag and with whole-byte keys: PA_NONE is then a refused row alone, whose place does not matter)
-        hipLaunchKernelGGL(pa_hist_kernel, dim3(sort_blocks), dim3(PA_THREADS), 0, ctx->stream, (const u32*)d_k[cur], (const u32*)d_v[cur], total, steps, ps, d_hist);
-        hipLaunchKernelGGL(pa_scan_kernel<0>, dim3(1), dim3(PA_THREADS), 0, ctx->stream, d_hist, sort_blocks * 256, (u32*)nullptr);
-        hipLaunchKernelGGL(pa_scatter_kernel, dim3(sort_blocks), dim3(PA_THREADS), 0, ctx->stream, (const u32*)d_k[cur], (const u32*)d_v[cur], d_k[cur ^ 1], d_v[cur ^ 1], total,
-                           steps, ps, (const u32*)d_hist);
-        e = hipGetLastError();
+        const PaSort sort = {d_k[cur], d_v[cur], d_k[cur ^ 1], d_v[cur ^ 1], ps};
+        e = count_pass(ctx, sort, total, plan, 256, d_hist, nullptr, nullptr);
         cur ^= 1;
     }
     if (e == hipSuccess) {
         hipLaunchKernelGGL(pa_heads_kernel, dim3(res_blocks), dim3(PA_THREADS), 0, ctx->stream, (const u32*)d_k[cur], (const u32*)d_v[cur], total, d_cnt, d_last);
-        hipLaunchKernelGGL(pa_scan_kernel<0>, dim3(1), dim3(PA_THREADS), 0, ctx->stream, d_cnt, res_blocks, &d_ctl->n_keys);
-        hipLaunchKernelGGL(pa_scan_kernel<1>, dim3(1), dim3(PA_THREADS), 0, ctx->stream, d_last, res_blocks, (u32*)nullptr);
+        hipLaunchKernelGGL(scan_kernel<0>, dim3(1), dim3(PA_THREADS), 0, ctx->stream, d_cnt, res_blocks, &d_ctl->n_keys);
+        hipLaunchKernelGGL(scan_kernel<1>, dim3(1), dim3(PA_THREADS), 0, ctx->stream, d_last, res_blocks, (u32*)nullptr);
         hipLaunchKernelGGL(pa_resolve_kernel, dim3(res_blocks), dim3(PA_THREADS), 0, ctx->stream, (const u32*)d_k[cur], (const u32*)d_v[cur], total, (const u32*)d_cnt,
                            (const u32*)d_last, (const PaStream*)d_st, (const u32*)d_base, n_streams, n_payload, (const u32* const*)d_pay, (u32* const*)d_prv, h_init, h_sum);
         e = hipGetLastError();

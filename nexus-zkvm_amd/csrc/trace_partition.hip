@@ -4,12 +4,9 @@
 // prover2/machine/src/components/execution/common/mod.rs:31-39): row i of the component is the i-th such step, the trace is padded to a
 // power of two with IsLocalPad = 1 (execution/add/mod.rs:157-183); the Cpu component takes every step (components/cpu/trace.rs:36-59).
 // That is a stable multi-way partition of the steps followed by a gather into bit-reversed circle-domain order:
-//   order      ONE 8-bit counting pass over the class column, three launches in the shape of prev_access.hip's sort pass: per-block class
-//              histogram, exclusive scan of the [class][block] counts (one block), stable placement order[class_start[c] + rank] = step.
-//              Inside a block a wave ranks its 64 steps with 8 ballots (the mask of the lanes that hold my class; rank = its popcount
-//              below my lane), so the long runs of one opcode an execution has are combined before they meet an LDS counter: one lane per
-//              distinct class and wave touches LDS, the placement uses plain LDS stores.  A step of class NX_PART_NONE is no element; a
-//              class word that is neither that nor below n_classes is no element either and leaves its step in a 32-bit minimum.
+//   order      ONE counting pass of count_pass.cuh over the class column (histogram, scan, stable placement) with the policy TpOrder:
+//              the digit is the class, n_classes histogram rows, order[class_start[c] + rank] = step.  A step of class NX_PART_NONE is no
+//              element; a class word that is neither that nor below n_classes is no element either and leaves its step in a 32-bit minimum.
 //   fill       one work-item per storage position of one destination: it derives its natural row r once, reads the row's step from the
 //              order (class_start + r; the row itself for NX_PART_ALL), loads every source word the destination uses ONCE and cuts all
 //              limbs of that word from the register.  The destination's descriptor, its limb specs and its column pointers are
@@ -25,14 +22,9 @@
 namespace nx {
 
 #include "trace_rows.h"
+#include "count_pass.cuh"
 
-constexpr u32 TP_THREADS = 256;
-// a block of the counting pass takes steps * 256 consecutive steps of the table: TP_MIN_STEPS tiles while that needs at most TP_MAX_BLOCKS
-// blocks, more tiles beyond (the host emulation builds with a cap of 2 to reach that path at a small size)
-#ifndef TP_MAX_BLOCKS
-#define TP_MAX_BLOCKS 1024
-#endif
-constexpr u32 TP_MIN_STEPS = 4, TP_MAX_ORDER_BLOCKS = TP_MAX_BLOCKS;
+constexpr u32 TP_THREADS = CP_THREADS;
 constexpr u32 TP_MAX_CLASSES = NX_PART_MAX_CLASSES, TP_MAX_STEPS = 1u << 30;
 constexpr size_t TP_MAX_TABLE_BYTES = (size_t)1 << 20;       // descriptors of one fill launch (a call with more is cut between destinations)
 
@@ -53,118 +45,23 @@ __device__ __forceinline__ void tp_store(u32* base, u32 byte_off, u32 w) { *(NX_
 __device__ __forceinline__ u32 tp_here(u32 off) { asm volatile("" : "+v"(off)); return off; }
 #endif
 
-// the lanes of this wave that hold class c (lanes without an element hold none and are in no mask)
-__device__ __forceinline__ u64 tp_match(u32 c, bool have) {
-    u64 m = __ballot(have);
-#pragma unroll
-    for (u32 b = 0; b < 8; b++) {
-        const bool bit = (c >> b) & 1;
-        const u64 bb = __ballot(bit);
-        m &= bit ? bb : ~bb;
+// the order as a counting pass: step j is an element if its class word is below n_classes; the histogram walk reports a word outside the
+// classes that is not NX_PART_NONE, the placement stores the step index
+struct TpOrder {
+    const u32* cls; u32 n_classes; u32* first_bad; u32* order;
+    typedef u32 Item;
+    __device__ __forceinline__ bool class_of(u32 j, u32 n_steps, u32* c, bool report) const {
+        *c = 0;
+        if (j >= n_steps) return false;
+        const u32 w = gld(cls + j);
+        if (w < n_classes) { *c = w; return true; }
+        if (report && w != NX_PART_NONE) atomicMin(first_bad, j);
+        return false;
     }
-    return m;
-}
-
-// the class of step j as an element of the partition; a word outside the classes that is not NX_PART_NONE is reported
-__device__ __forceinline__ bool tp_class_of(const u32* __restrict__ cls, u32 j, u32 n_steps, u32 n_classes, u32* c, u32* first_bad) {
-    if (j >= n_steps) { *c = 0; return false; }
-    const u32 w = gld(cls + j);
-    if (w < n_classes) { *c = w; return true; }
-    if (first_bad && w != NX_PART_NONE) atomicMin(first_bad, j);
-    *c = 0;
-    return false;
-}
-
-// hist[class * blocks + block]: steps of the block's tile with that class
-__global__ __launch_bounds__(TP_THREADS) void tp_hist_kernel(const u32* __restrict__ cls, u32 n_steps, u32 steps, u32 n_classes, u32* __restrict__ hist, TpCtl* __restrict__ ctl) {
-    __shared__ u32 h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const u32 lane = threadIdx.x & 63;
-    for (u32 st = 0; st < steps; st++) {
-        const u32 j = (blockIdx.x * steps + st) * TP_THREADS + threadIdx.x;
-        u32 c;
-        const bool have = tp_class_of(cls, j, n_steps, n_classes, &c, &ctl->first_bad);
-        const u64 m = tp_match(c, have);
-        if (have && !(m & (((u64)1 << lane) - 1))) atomicAdd(&h[c], (u32)__popcll(m));      // the lowest lane of every class of the wave
-    }
-    __syncthreads();
-    if (threadIdx.x < n_classes) hist[threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
-}
-
-// exclusive sum of one value per thread over the block's 256 threads, *total: over the whole block.  lds: 4 words, free again on return.
-__device__ __forceinline__ u32 tp_block_scan(u32 v, u32* lds, u32* total) {
-    const u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    u32 inc = v;
-#pragma unroll
-    for (u32 off = 1; off < 64; off <<= 1) {
-        const u32 t = __shfl(inc, (int)((lane - off) & 63), 64);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    u32 base = 0, tot = 0;
-#pragma unroll
-    for (u32 i = 0; i < 4; i++) { const u32 x = lds[i]; if (i < w) base += x; tot += x; }
-    __syncthreads();
-    const u32 prev = __shfl(inc, (int)((lane - 1) & 63), 64);
-    *total = tot;
-    return lane ? base + prev : base;
-}
-
-// in-place exclusive sum of a[0 .. n) by ONE block; *total_out: the sum over everything
-__global__ __launch_bounds__(TP_THREADS) void tp_scan_kernel(u32* __restrict__ a, u32 n, u32* __restrict__ total_out) {
-    __shared__ u32 lds[4];
-    u32 carry = 0;
-    for (u32 base = 0; base < n; base += TP_THREADS * 4) {
-        const u32 i = base + threadIdx.x * 4;
-        u32 x[4];
-#pragma unroll
-        for (u32 e = 0; e < 4; e++) x[e] = i + e < n ? gld(a + i + e) : 0u;
-        const u32 s1 = x[0] + x[1], s2 = s1 + x[2], s3 = s2 + x[3];
-        u32 tot;
-        const u32 run = carry + tp_block_scan(s3, lds, &tot);
-        const u32 out[4] = {run, run + x[0], run + s1, run + s2};
-#pragma unroll
-        for (u32 e = 0; e < 4; e++) if (i + e < n) gst(a + i + e, out[e]);
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total_out = carry;
-}
-
-// offs: the scanned histogram.  Steps leave in the order they came in: by tile, by wave, by lane.
-__global__ __launch_bounds__(TP_THREADS) void tp_place_kernel(const u32* __restrict__ cls, u32 n_steps, u32 steps, u32 n_classes, const u32* __restrict__ offs,
-                                                              u32* __restrict__ order, TpCtl* __restrict__ ctl) {
-    __shared__ u32 run[256];            // next free slot of every class
-    __shared__ u32 wc[2][4][256];       // per tile parity and wave: steps with the class (zero outside the tile that fills it)
-    const u32 first = threadIdx.x < n_classes ? offs[threadIdx.x * gridDim.x + blockIdx.x] : 0u;
-    run[threadIdx.x] = first;
-    if (blockIdx.x == 0 && threadIdx.x < n_classes) ctl->start[threadIdx.x] = first;         // where the class begins in the order
-    for (u32 i = 0; i < 8; i++) (&wc[0][0][0])[i * 256 + threadIdx.x] = 0;
-    __syncthreads();
-    const u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (u32 st = 0; st < steps; st++) {
-        const u32 par = st & 1;
-        const u32 j = (blockIdx.x * steps + st) * TP_THREADS + threadIdx.x;
-        u32 c;
-        const bool have = tp_class_of(cls, j, n_steps, n_classes, &c, nullptr);
-        const u64 m = tp_match(c, have);
-        const u32 rank = (u32)__popcll(m & (((u64)1 << lane) - 1));
-        if (have && rank == 0) wc[par][w][c] = (u32)__popcll(m);
-        __syncthreads();
-        if (have) {
-            u32 o = run[c] + rank;
-            for (u32 i = 0; i < w; i++) o += wc[par][i][c];
-            gst(order + o, j);
-        }
-        __syncthreads();
-        const u32 s = wc[par][0][threadIdx.x] + wc[par][1][threadIdx.x] + wc[par][2][threadIdx.x] + wc[par][3][threadIdx.x];
-        if (s) {   // thread t owns class t; these words are next written two tiles on, next read after the coming barrier
-            run[threadIdx.x] += s;
-            wc[par][0][threadIdx.x] = 0; wc[par][1][threadIdx.x] = 0; wc[par][2][threadIdx.x] = 0; wc[par][3][threadIdx.x] = 0;
-        }
-    }
-}
+    __device__ __forceinline__ bool digit(u32 j, u32 n_steps, u32* c) const { return class_of(j, n_steps, c, true); }
+    __device__ __forceinline__ bool load(u32 j, u32 n_steps, Item* it, u32* c) const { *it = j; return class_of(j, n_steps, c, false); }
+    __device__ __forceinline__ void store(u32 slot, const Item& it) const { gst(order + slot, it); }
+};
 
 // last index i < n with a[i] <= x (a ascending, a[0] <= x); a and x are uniform over the block
 __device__ __forceinline__ u32 tp_find(const u32* a, u32 n, u32 x) {
@@ -243,10 +140,9 @@ int nx_trace_partition_create(nx_ctx* ctx, const uint32_t* d_class, uint32_t n_s
     p->ctx = ctx; p->d_class = d_class; p->n_steps = n_steps; p->n_classes = n_classes; p->d_order = nullptr;
     p->start.assign(n_classes + 1, 0);
     if (n_steps) {
-        const u32 steps = std::max<u32>(TP_MIN_STEPS, (u32)(((u64)n_steps + (u64)TP_THREADS * TP_MAX_ORDER_BLOCKS - 1) / ((u64)TP_THREADS * TP_MAX_ORDER_BLOCKS)));
-        const u32 blocks = (u32)(((u64)n_steps + (u64)steps * TP_THREADS - 1) / ((u64)steps * TP_THREADS));
+        const CountPlan plan = count_plan(n_steps);
         auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        const size_t b_ctl = al(sizeof(TpCtl)), b_hist = al((size_t)n_classes * blocks * 4);
+        const size_t b_ctl = al(sizeof(TpCtl)), b_hist = al((size_t)n_classes * plan.blocks * 4);
         NX_TRY(dev_alloc(ctx, (size_t)n_steps * 4, (void**)&p->d_order));
         uint8_t* blob = nullptr;
         int rc = dev_alloc(ctx, b_ctl + b_hist, (void**)&blob);
@@ -256,11 +152,8 @@ int nx_trace_partition_create(nx_ctx* ctx, const uint32_t* d_class, uint32_t n_s
         rc = upload_async_staged(ctx, d_ctl, &h_ctl, sizeof h_ctl);
         hipError_t e = hipSuccess;
         if (rc == NX_OK) {
-            hipLaunchKernelGGL(tp_hist_kernel, dim3(blocks), dim3(TP_THREADS), 0, ctx->stream, (const u32*)d_class, n_steps, steps, n_classes, d_hist, d_ctl);
-            hipLaunchKernelGGL(tp_scan_kernel, dim3(1), dim3(TP_THREADS), 0, ctx->stream, d_hist, n_classes * blocks, &d_ctl->total);
-            hipLaunchKernelGGL(tp_place_kernel, dim3(blocks), dim3(TP_THREADS), 0, ctx->stream, (const u32*)d_class, n_steps, steps, n_classes, (const u32*)d_hist, d_order,
-                               d_ctl);
-            e = hipGetLastError();
+            const TpOrder order = {d_class, n_classes, &d_ctl->first_bad, d_order};
+            e = count_pass(ctx, order, n_steps, plan, n_classes, d_hist, &d_ctl->total, d_ctl->start);
             if (e == hipSuccess) rc = copy_d2h_blocking(ctx, &h_ctl, d_ctl, sizeof h_ctl);
         }
         // The copy above blocks, so every launch has completed.  Where a launch failed the copy is skipped and earlier kernels may still

@@ -56,6 +56,12 @@ inline unsigned long long atomicExch(unsigned long long* p, unsigned long long v
 template <class T> inline T atomicMin(T* p, T v) { T o = __atomic_load_n(p, __ATOMIC_RELAXED); while (v < o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {} return o; }
 inline u32 gld(const u32* p) { return *p; }
 inline uint4 gld4(const u32* p) { if ((uintptr_t)p & 15) { fprintf(stderr, "misaligned gld4\n"); abort(); } return {p[0], p[1], p[2], p[3]}; }
+inline uint4 gld4_guarded(const u32* col, u32 row, u32 n, bool vec) {
+    if (vec) return gld4(col + row);
+    const auto at = [&](u32 i) { return i < n ? col[i] : 0u; };
+    return {at(row), at(row + 1), at(row + 2), at(row + 3)};
+}
+struct PackedKey { u32 n_cols, bits[4], shift[4], total_bits; };
 inline void gst(u32* p, u32 v) { *p = v; }
 
 typedef int hipError_t; constexpr hipError_t hipSuccess = 0;

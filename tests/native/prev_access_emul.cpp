@@ -1,8 +1,9 @@
 // nx_trace_prev_access on the host: csrc/prev_access.hip compiled as plain C++ against tests/native/prev_emul/internal.h (256 lock-step
 // threads per block as fibers, waves of 64 with ballot / shuffle, LDS as static storage), so the entry point with its kernels is checked
 // against a sequential walk over a map — under the address and undefined-behaviour sanitizers, which watch every LDS, histogram and
-// scatter index.
-#include "prev_access_emu.cpp"   // a copy of csrc/prev_access.hip next to the shim internal.h and trace_rows.h (the test makes it)
+// placement index.  Built twice by the test: as it is, and with -DNX_COUNT_PASS_MAX_BLOCKS=2, where a block of the sort takes more tiles
+// than the minimum.
+#include "prev_access_emu.cpp"   // a copy of csrc/prev_access.hip next to the shim internal.h, trace_rows.h and count_pass.cuh (the test makes it)
 #include <random>
 #include <map>
 
@@ -185,6 +186,16 @@ int main() {
             run_case("  and in the stream without flags", st, bits, 5, init, false, ~0u, NX_ERR_PROTOCOL);
         }
     }
+    {   // 2^11 + 2 elements: with a block cap of 2 (the test's second build) a sort block takes five tiles, one more than the minimum, in
+        // every one of the two passes (13 key bits and flags); as built it is two blocks of four tiles and one of one
+        const std::vector<u32> bits{8, 5}, init{P - 3};
+        std::vector<Stream> st;
+        st.push_back(make_stream(bits, 11, 1, 0, true, 0)); st.back().linear = 1;
+        st.push_back(make_stream(bits, 1, 1, 0, false, 0)); st.back().linear = 1;
+        const CountPlan plan = count_plan(((u64)1 << 11) + 2);
+        const bool reached = CP_MAX_BLOCKS != 2 || (plan.tiles > CP_MIN_TILES && plan.blocks == 2);
+        run_case(reached ? "  linear streams of 2^11 and 2 rows" : "  linear streams of 2^11 and 2 rows: PLAN NOT REACHED", st, bits, 1, init, true, ~0u, reached ? NX_OK : -99);
+    }
     {   // refusal: an output that is also an input
         std::vector<u32> bits{5}, init{0}; std::vector<u32> col(4, 1), out(4, 0);
         const u32* kp[1] = {col.data()}; const u32* pp[1] = {col.data()}; u32* vp[1] = {col.data()};
@@ -195,6 +206,6 @@ int main() {
         printf("%-58s rc %d %s  %s\n", "aliased output", rc, ok ? "OK" : "FAIL", ctx.err.c_str());
         ok ? n_ok++ : n_fail++;
     }
-    printf("%d cases OK\n%d failures\n", n_ok, n_fail);
+    printf("block cap %u\n%d cases OK\n%d failures\n", (unsigned)CP_MAX_BLOCKS, n_ok, n_fail);
     return n_fail != 0;
 }

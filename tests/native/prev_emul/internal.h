@@ -126,6 +126,12 @@ inline u32 atomicAdd(u32* p, u32 v) { const u32 o = *p; *p = o + v; return o; } 
 template <class T> inline T atomicMin(T* p, T v) { const T o = *p; if (v < o) *p = v; return o; }
 inline u32 gld(const u32* p) { return *p; }
 inline uint4 gld4(const u32* p) { if ((uintptr_t)p & 15) { fprintf(stderr, "misaligned gld4\n"); abort(); } return {p[0], p[1], p[2], p[3]}; }
+inline uint4 gld4_guarded(const u32* col, u32 row, u32 n, bool vec) {
+    if (vec) return gld4(col + row);
+    const auto at = [&](u32 i) { return i < n ? col[i] : 0u; };
+    return {at(row), at(row + 1), at(row + 2), at(row + 3)};
+}
+struct PackedKey { u32 n_cols, bits[4], shift[4], total_bits; };
 inline void gst(u32* p, u32 v) { *p = v; }
 inline void gst4(u32* p, uint4 v) { if ((uintptr_t)p & 15) { fprintf(stderr, "misaligned gst4\n"); abort(); } p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w; }
 

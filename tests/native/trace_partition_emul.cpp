@@ -2,9 +2,9 @@
 // (tests/native/prev_emul/internal.h with tests/native/part_emul/shim.h on top), so the entry points with their kernels are compared
 // word for word with a sequential filter-and-enumerate walk over the step table — under the address and undefined-behaviour
 // sanitizers, which watch every LDS, histogram, order and descriptor index.  Built twice by the test: as it is, and with
-// -DTP_MAX_BLOCKS=2, where a block of the counting pass takes more tiles than the minimum.
+// -DNX_COUNT_PASS_MAX_BLOCKS=2, where a block of the counting pass takes more tiles than the minimum.
 #include "shim.h"
-#include "trace_partition_emu.cpp"   // a copy of csrc/trace_partition.hip next to the shim and trace_rows.h (the test makes it)
+#include "trace_partition_emu.cpp"   // a copy of csrc/trace_partition.hip next to the shim, trace_rows.h and count_pass.cuh (the test makes it)
 #include <random>
 
 static std::mt19937_64 rng(7102);
@@ -79,7 +79,7 @@ static bool run_case(u32 n, u32 k, Dist dist, u32 extra_log, bool opt_cols, cons
     if (rc != NX_OK || !part) { printf("   create: rc %d %s\n", rc, ctx.err.c_str()); report(false, name); return false; }
     for (u32 c = 0; c < k; c++) if (counts[c] != rows[c].size()) { printf("   count of class %u: %u, %zu expected\n", c, counts[c], rows[c].size()); ok = false; }
     if (ctx.live != (n ? 1u : 0u) || ctx.live_bytes != (size_t)n * 4) { printf("   live after create: %zu blocks %zu bytes\n", ctx.live, ctx.live_bytes); ok = false; }
-    if (ctx.peak_bytes > (size_t)n * 4 + 4 * (size_t)k * TP_MAX_ORDER_BLOCKS + 1280 + 256) { printf("   peak %zu bytes above the header's bound\n", ctx.peak_bytes); ok = false; }
+    if (ctx.peak_bytes > (size_t)n * 4 + 4 * (size_t)k * CP_MAX_BLOCKS + 1280 + 256) { printf("   peak %zu bytes above the header's bound\n", ctx.peak_bytes); ok = false; }
 
     // every class and NX_PART_ALL; class 0 twice (two destinations of one class in one call)
     std::vector<Dest> dests;
@@ -226,6 +226,6 @@ int main() {
     refused_class(40);
     refused_class(0xFFFFFFFEu);
     refused_fill();
-    printf("block cap %u\n%d failures, %d passed\n", (unsigned)TP_MAX_ORDER_BLOCKS, n_fail, n_ok);
+    printf("block cap %u\n%d failures, %d passed\n", (unsigned)CP_MAX_BLOCKS, n_fail, n_ok);
     return n_fail ? 1 : 0;
 }

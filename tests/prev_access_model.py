@@ -29,6 +29,66 @@ def to_storage(natural, log_size):
     return natural[rows_of_positions(log_size, False)]
 
 
+def two_linear_streams(rng, log_size):
+    """one epoch: a linear stream of 2^log_size rows with flags and one of 2 rows without, key entries of 8 and 5 bits, one payload
+    column, every output wanted.  At 2^20 rows a block of the sort takes five tiles, one more than the minimum."""
+    streams = []
+    for log, flags in ((log_size, True), (1, False)):
+        n = 1 << log
+        streams.append({"key": [rng.integers(0, 256, n, dtype=np.uint32), rng.integers(0, 32, n, dtype=np.uint32)],
+                        "flag": rng.integers(0, 3, n, dtype=np.uint32) * rng.integers(1, 9, n, dtype=np.uint32) if flags else None,
+                        "payload": [rng.integers(0, P, n, dtype=np.uint32)], "log_size": log, "epoch": 0, "linear": True, "prev_wanted": [True], "want_ord": True})
+    return streams
+
+
+def model_by_sorting(streams, key_bits, n_payload, init=None):
+    """What model() returns, for sizes its Python walk is too slow for, from the definition in array form: the accepted accesses in time
+    order (epoch, natural row, stream), numpy's stable sort by key, then every element takes the payload of the one before it in its
+    run (init at the head) and its place in the run.  tests/test_prev_access_cpu.py holds it to model()."""
+    init = np.zeros(n_payload, np.uint32) if init is None else np.asarray(init, np.uint32)
+    epoch, row, sid, key, use, oor_at, pay = [], [], [], [], [], [], [[] for _ in range(n_payload)]
+    for s, st in enumerate(streams):
+        n = 1 << st["log_size"]
+        k, oor, shift = np.zeros(n, np.uint64), np.zeros(n, bool), 0
+        for col, b in zip(st["key"], key_bits):
+            x = np.asarray(col).astype(np.uint64)
+            oor |= x >= np.uint64(1 << b)
+            k |= x << np.uint64(shift)
+            shift += b
+        acc = np.ones(n, bool) if st.get("flag") is None else np.asarray(st["flag"]) != 0
+        epoch.append(np.full(n, int(st.get("epoch", 0)), np.int64))
+        row.append(rows_of_positions(st["log_size"], st.get("linear", False)))
+        sid.append(np.full(n, s, np.int64))
+        key.append(k)
+        use.append(acc & ~oor)
+        oor_at += [(s, int(p)) for p in np.flatnonzero(acc & oor)[:1]]
+        p = st.get("payload") or [None] * n_payload
+        for c in range(n_payload):
+            pay[c].append(np.zeros(n, np.uint32) if p[c] is None else np.asarray(p[c], np.uint32))
+    epoch, row, sid, key, use = (np.concatenate(a) for a in (epoch, row, sid, key, use))
+    pay = [np.concatenate(a) for a in pay]
+    t = np.lexsort((sid, row, epoch))                       # time order: the last key is the first criterion
+    t = t[use[t]]
+    o = t[np.argsort(key[t], kind="stable")]                # by key, in time order inside a key
+    ks, m = key[o], len(o)
+    head, tail = np.ones(m, bool), np.ones(m, bool)
+    head[1:] = ks[1:] != ks[:-1]
+    tail[:-1] = head[1:]
+    at = np.arange(m, dtype=np.int64)
+    place = at - np.maximum.accumulate(np.where(head, at, 0))
+    ends = np.cumsum([0] + [1 << st["log_size"] for st in streams])
+    cut = lambda a: [a[ends[s]:ends[s + 1]] for s in range(len(streams))]
+    prev = []
+    for c in range(n_payload):
+        moved, out = pay[c][o], np.zeros(len(key), np.uint32)
+        out[o] = np.where(head, init[c], np.concatenate([moved[:1], moved[:-1]]))
+        prev.append(cut(out))
+    ordinal = np.zeros(len(key), np.uint32)
+    ordinal[o] = place
+    return {"prev": [[prev[c][s] for c in range(n_payload)] for s in range(len(streams))], "ordinal": cut(ordinal), "keys": ks[head].astype(np.uint32),
+            "counts": (place[tail] + 1).astype(np.uint32), "last": [pay[c][o][tail] for c in range(n_payload)], "bad": min(oor_at) if oor_at else None}
+
+
 def model(streams, key_bits, n_payload, init=None):
     """streams: dicts of HOST arrays in storage order — key: one array per key column; log_size; optional flag (None: every row
     accesses), payload (n_payload arrays, None entries read as 0), epoch, linear.  Returns a dict: prev[s][c] / ordinal[s]: the

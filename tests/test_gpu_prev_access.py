@@ -2,7 +2,8 @@
 equality of words.
 1. key shapes [5] (one radix pass), [8, 5] (two), [8, 8, 8, 8] (four; five with flags) and [31]; 2^1, 2^2, 2^6, 2^11 and 2^14 rows (two
    rows, the tail of a tile, several blocks, the wrap between the halves of the circle domain); one, three and four streams; with and
-   without flags, ordinal and summary; 1, 5, 8 and 16 payload columns, some payload and output entries NULL;
+   without flags, ordinal and summary; 1, 5, 8 and 16 payload columns, some payload and output entries NULL; 2^20 + 2 rows, where a block of
+   the sort takes more than its minimum of tiles;
 2. skew;  3. epochs and mixed sizes;  4. the summary;  5. a key entry out of its bits;  6. determinism and memory;
 7. a register-file-shaped statement through a prover session: narrow seed columns, timestamps from nx_trace_program, previous-access
    columns and the final-state table from nx_trace_prev_access; the memory-check logup cancels, the statement is proved and verified."""
@@ -142,6 +143,18 @@ def test_exact_against_the_model(be, nz, key_bits, log_size):
                                    want_ord=want_ord or s == 0))
     init = rng.integers(0, P, size=n_payload, dtype=np.uint32)
     run(be, nz, streams, key_bits, n_payload, init, cap=(n_streams << log_size) if with_summary else None)
+
+
+def test_a_sort_block_of_more_than_the_minimum_tiles(be, nz):
+    """2^20 + 2 elements in one epoch: more than 1024 blocks of four tiles, so a block of each of the two sort passes takes five (the path
+    the host emulation reaches with a block cap of 2).  Judged by M.model_by_sorting, which tests/test_prev_access_cpu.py holds to the
+    sequential model."""
+    streams = M.two_linear_streams(np.random.default_rng(2020), 20)
+    key_bits, init = [8, 5], np.array([P - 3], np.uint32)
+    want = M.model_by_sorting(streams, key_bits, 1, init)
+    assert want["bad"] is None and len(want["keys"]) == 1 << 13
+    d = Device(be, nz, streams, 1, cap=1 << 13)
+    d.check(want, d.call(key_bits, init))
 
 
 @pytest.mark.parametrize("key_bits", [[8, 5], [8, 8, 8, 8]], ids=["bits8_5", "bits8_8_8_8"])

@@ -170,9 +170,10 @@ def test_kernels_in_lock_step_on_the_host_under_sanitizers(tmp_path):
     csrc = os.path.join(ROOT, "nexus-zkvm_amd", "csrc")
     shutil.copy(os.path.join(csrc, "trace_partition.hip"), str(tmp_path / "trace_partition_emu.cpp"))
     shutil.copy(os.path.join(csrc, "trace_rows.h"), str(tmp_path / "trace_rows.h"))
+    shutil.copy(os.path.join(csrc, "count_pass.cuh"), str(tmp_path / "count_pass.cuh"))
     shutil.copy(os.path.join(native, "prev_emul", "internal.h"), str(tmp_path / "internal.h"))
     shutil.copy(os.path.join(native, "part_emul", "shim.h"), str(tmp_path / "shim.h"))
-    for cap, flags in ((1024, []), (2, ["-DTP_MAX_BLOCKS=2"])):
+    for cap, flags in ((1024, []), (2, ["-DNX_COUNT_PASS_MAX_BLOCKS=2"])):
         exe = str(tmp_path / ("trace_partition_emul_%d" % cap))
         subprocess.run([gxx, "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-pthread", "-Wno-unknown-pragmas"] + flags +
                        ["-I" + str(tmp_path), "-I" + os.path.join(ROOT, "include"), os.path.join(native, "trace_partition_emul.cpp"), "-o", exe], check=True, capture_output=True)
