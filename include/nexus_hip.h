@@ -15,6 +15,24 @@
  *  - Pointers named `d_*` / documented "device" are HIP device pointers (from nx_alloc, or any
  *    hipMalloc'd / torch-allocated memory on the context's device).  Pointer *arrays* such as
  *    `const uint32_t* const* cols` are HOST arrays holding device pointers.
+ *  - ALIGNMENT.  A device column may lie at any 4-byte aligned address (a pointer into a slab, `ptr + k * len`, a row block), with these
+ *    exceptions, whose kernels read and write 16 or 8 bytes at a time with no word path: a misaligned pointer is refused with NX_ERR_ARG
+ *    before anything is launched — nx_last_error names the argument and the column index — and the context stays usable.
+ *      16 bytes: the columns of nx_interpolate_batch (d_cols), nx_evaluate_batch (d_polys, d_out), nx_lde_batch / nx_lde_commit (d_cols,
+ *      d_lde) and nx_commit_root (d_cols), nx_accumulate_quotients / nx_accumulate_quotients_partial (d_cols, d_out4); the node buffers
+ *      of nx_merkle_commit_on_layer (d_prev_layer, d_out) and nx_merkle_leaf_chain (d_state_in, d_state_out).  The columns these two
+ *      hash (d_cols) are read word by word and may lie anywhere.
+ *      8 bytes: d_src4 of nx_fold_circle_into_line and nx_fold_line (a lane reads its pair as one word; the destinations are word
+ *      accesses), the 64-bit side of nx_m31_widen (d_dst) and nx_m31_narrow (d_src).
+ *    A column shorter than the access is exempt, it goes through a word kernel: transforms of 2 or 4 rows — nx_interpolate_batch below
+ *    2^3 rows, the source of nx_evaluate_batch / nx_lde_batch / nx_commit_root below 2^2, an extension (d_out, d_lde) below 2^3 — and
+ *    quotients of 2 rows.  So the 2-row columns nx_prover_tree_begin packs into one slab and the packed coordinates of 1- and 2-word
+ *    secure columns are fine as they are.  nx_trace_keccak_round and nx_trace_keccak_memory_check state the same kind of rule for their
+ *    d_states / d_states_out (8 bytes) and d_timestamps (16 bytes) themselves; their trace columns are written word by word.
+ *    Entries whose host code chooses between a 16-byte and a word kernel by the pointers' low bits accept any word-aligned pointer and
+ *    give the same words either way: nx_copy, nx_merkle_commit, nx_merkle_from_leaves, nx_upload_columns_narrow,
+ *    nx_logup_multiplicities, nx_trace_prev_access, nx_trace_program.  Every other entry touches caller memory word by word.
+ *    tests/placement.py classifies every entry with the source lines; tests/test_gpu_placement.py runs each at every word offset.
  *  - Every function returns NX_OK (0) or a negative error code; nx_last_error() gives the text.
  *    Allocation failure is an error code, not a panic (reference: vec![] aborts, trace_builder.rs:29).
  *  - A context is single-threaded at the protocol level like the reference's prover
@@ -112,7 +130,8 @@ int nx_memset_zero(nx_ctx* ctx, uint32_t* d_ptr, size_t n_words);
 int nx_upload(nx_ctx* ctx, uint32_t* d_dst, const uint32_t* h_src, size_t n_words);
 int nx_download(nx_ctx* ctx, uint32_t* h_dst, const uint32_t* d_src, size_t n_words);
 /* Column::clone on device (the reference clones whole traces before committing them: prover/src/machine.rs:210-214,232;
- * prover2/trace/src/component.rs:75).  Stream-ordered; src and dst must not overlap. */
+ * prover2/trace/src/component.rs:75).  Stream-ordered; src and dst must not overlap.  Any word-aligned pointers and any length: 16-byte
+ * copies when both pointers are 16-byte aligned and n_words is a multiple of 4, a plain device copy otherwise. */
 int nx_copy(nx_ctx* ctx, uint32_t* d_dst, const uint32_t* d_src, size_t n_words);
 /* Gather scattered words: out[i] = d_ptrs[i][index[i]] (decommitment reads, MerkleProver::decommit). */
 int nx_gather(nx_ctx* ctx, const uint32_t* const* d_ptrs, const uint64_t* index, size_t n, uint32_t* h_out);
@@ -154,7 +173,8 @@ int nx_host_unpin(nx_ctx* ctx, const void* h);
  * and nx_last_error names the kind, the value, the column (index into h_cols) and the row (index into that column) — the lowest
  * column, then row, whatever the thread count; the chunk that holds it is never sent, the caller's arrays are never written and the
  * context stays usable.  A call whose columns are all NX_COL_U32 is nx_upload_columns.  Blocking: the host columns are free on return.
- * NX_ERR_ARG for NULL arguments, zero columns or an unknown kind. */
+ * NX_ERR_ARG for NULL arguments, zero columns or an unknown kind.  d_cols: any word-aligned pointers (a column that is not 16-byte aligned
+ * is widened one value per lane). */
 int nx_upload_columns_narrow(nx_ctx* ctx, const void* const* h_cols, const uint8_t* kinds, uint32_t n_cols, uint32_t log_size,
                              uint32_t* const* d_cols, int coset_order);
 
@@ -189,7 +209,8 @@ int nx_eval_at_points(nx_ctx* ctx, const uint32_t* const* d_polys, uint32_t log_
 
 /* ------------------------------------------- K5/K6: MerkleOps<Blake2sMerkleHasher> --------- */
 /* MerkleProver::commit -> MerkleOps::commit_on_layer per layer (reference machine.rs:228,237,263).
- * Columns in commit order (stable-sorted by size inside); log_sizes are the column (LDE) sizes. */
+ * Columns in commit order (stable-sorted by size inside); log_sizes are the column (LDE) sizes.  Any word-aligned column pointers: the
+ * fused launch ("merkle.fused") is taken only when every column is 16-byte aligned, the per-level kernels read words. */
 int nx_merkle_commit(nx_ctx* ctx, const uint32_t* const* d_cols, const uint32_t* log_sizes, uint32_t n_cols,
                      nx_tree** out);
 int nx_merkle_root(nx_ctx* ctx, const nx_tree* tree, uint8_t root[32]); /* roots(): machine.rs:411 */
@@ -225,7 +246,8 @@ int nx_merkle_leaf_chain(nx_ctx* ctx, const uint32_t* const* d_cols, uint32_t n_
                          uint32_t col_offset, uint32_t total_cols, const uint32_t* d_state_in, uint32_t* d_state_out,
                          uint64_t row_begin, uint64_t n_rows);
 /* MerkleProver over already hashed leaves: builds the inner layers above 2^log_size leaf digests (8 words each,
- * copied in) — the part of a sharded commit the last GPU of the chain runs before broadcasting the root. */
+ * copied in, nx_copy's rule: any word-aligned pointer) — the part of a sharded commit the last GPU of the chain runs before broadcasting
+ * the root. */
 int nx_merkle_from_leaves(nx_ctx* ctx, const uint32_t* d_leaf_digests, uint32_t log_size, nx_tree** out);
 
 /* ------------------------------------------------------------- K8: QuotientOps ------------- */
@@ -856,7 +878,7 @@ int nx_logup_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_instr, ui
  * its values, "use 2 row position 17: (300) is not a row of the table"; d_mult is filled for the rows that are present.
  * Key spaces of up to 2^NX_MULT_LDS_MAX_KEY_BITS keys are counted in block-private LDS counters, wider ones with global atomics.
  * Blocking (it reports a count); temporaries (8 bytes per key of the key space) come from the context's allocator and are released
- * before it returns. */
+ * before it returns.  Every column may lie at any word-aligned address (a use whose columns are not all 16-byte aligned is read word by word). */
 #define NX_MULT_LDS_MAX_KEY_BITS 12
 typedef struct nx_lookup_use {
     const uint32_t* const* d_values;  /* n_key_cols device columns, 2^log_size canonical M31 words each, ANY row order */
@@ -903,7 +925,8 @@ int nx_logup_multiplicities(nx_ctx* ctx, const nx_lookup_use* uses, uint32_t n_u
  * (two (key, handle) buffers of 8 A each, the per-block digit counts, A at most and never above 1 MiB, A / 128 for the run heads) and NOTHING per
  * distinct key: the summary goes straight into the caller's arrays.  Taken from the context's allocator, released before the call
  * returns.  Blocking.  ceil(sum of key_bits / 8) sort passes, one more when some stream has a d_flag and the sum is a multiple of 8
- * (rows that do not access sort behind the largest key). */
+ * (rows that do not access sort behind the largest key).  Every column may lie at any word-aligned address (a stream whose columns are not
+ * all 16-byte aligned is read and written word by word). */
 typedef struct nx_access_stream {
     const uint32_t* const* d_key;      /* n_key_cols columns, 2^log_size canonical words                      */
     const uint32_t* d_flag;            /* NULL: every row is an access; else the row accesses iff word != 0   */

@@ -143,6 +143,7 @@ int nx_merkle_commit_on_layer(nx_ctx* ctx, uint32_t log_size, const uint32_t* d_
     NX_GUARD(ctx);
     if (!ctx || !d_out || (n_cols && !d_cols)) return set_err(ctx, NX_ERR_ARG, "nx_merkle_commit_on_layer: NULL argument");
     if (log_size > 30) return set_err(ctx, NX_ERR_ARG, "nx_merkle_commit_on_layer: layer too large");
+    { const void* p[2] = {d_prev_layer, d_out}; NX_TRY(check_aligned(ctx, "nx_merkle_commit_on_layer", "d_prev_layer", p, 1, 16, -1)); NX_TRY(check_aligned(ctx, "nx_merkle_commit_on_layer", "d_out", p + 1, 1, 16, -1)); }
     ColSet cs; NX_TRY(make_colset(ctx, d_cols, n_cols, &cs));
     return merkle_layer(ctx, cs, n_cols, d_prev_layer, d_out, log_size);
 }

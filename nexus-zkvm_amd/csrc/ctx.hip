@@ -138,6 +138,17 @@ int make_colset(nx_ctx* ctx, const uint32_t* const* h_ptrs, uint32_t n, ColSet* 
     return NX_OK;
 }
 
+int check_aligned(nx_ctx* ctx, const char* entry, const char* arg, const void* const* h_ptrs, uint32_t n, uint32_t align, int64_t first_index) {
+    uintptr_t all = 0;
+    for (uint32_t i = 0; i < n; i++) all |= (uintptr_t)h_ptrs[i];
+    if (!(all & (align - 1))) return NX_OK;
+    uint32_t i = 0;
+    while (!((uintptr_t)h_ptrs[i] & (align - 1))) i++;
+    const std::string idx = first_index < 0 ? std::string() : "[" + std::to_string(first_index + i) + "]";
+    return set_err(ctx, NX_ERR_ARG, std::string(entry) + ": " + arg + idx + " must be " + std::to_string(align) + "-byte aligned (the kernel reads and writes it in " +
+                                        std::to_string(align) + "-byte words)");
+}
+
 int dev_alloc(nx_ctx* ctx, size_t bytes, void** out) {
     if (bytes == 0) bytes = 4;
     bytes = (bytes + 255) & ~(size_t)255;
@@ -519,6 +530,7 @@ int nx_m31_add_into(nx_ctx* ctx, uint32_t* d_dst, const uint32_t* d_src, size_t 
 int nx_m31_widen(nx_ctx* ctx, uint64_t* d_dst, const uint32_t* d_src, size_t n_words) {
     NX_GUARD(ctx);
     if (!n_words) return NX_OK;
+    { const void* p = d_dst; NX_TRY(check_aligned(ctx, "nx_m31_widen", "d_dst", &p, 1, 8, -1)); }
     hipLaunchKernelGGL(m31_widen_kernel, dim3(stream_grid(ctx, n_words)), dim3(256), 0, ctx->stream, (u64*)d_dst, d_src, n_words);
     NX_LAUNCH_CHECK(ctx);
     return NX_OK;
@@ -526,6 +538,7 @@ int nx_m31_widen(nx_ctx* ctx, uint64_t* d_dst, const uint32_t* d_src, size_t n_w
 int nx_m31_narrow(nx_ctx* ctx, uint32_t* d_dst, const uint64_t* d_src, size_t n_words) {
     NX_GUARD(ctx);
     if (!n_words) return NX_OK;
+    { const void* p = d_src; NX_TRY(check_aligned(ctx, "nx_m31_narrow", "d_src", &p, 1, 8, -1)); }
     hipLaunchKernelGGL(m31_narrow_kernel, dim3(stream_grid(ctx, n_words)), dim3(256), 0, ctx->stream, d_dst, (const u64*)d_src, n_words);
     NX_LAUNCH_CHECK(ctx);
     return NX_OK;

@@ -584,6 +584,7 @@ int nx_twiddles_download(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* h_tw, uin
 int nx_interpolate_batch(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, uint32_t n_cols, uint32_t log_size) {
     NX_GUARD(ctx);
     if (n_cols == 0) return NX_OK;
+    if (log_size >= 3) NX_TRY(check_aligned(ctx, "nx_interpolate_batch", "d_cols", (const void* const*)d_cols, n_cols, 16));   // 2^1 / 2^2 rows: fft_tiny_kernel, words
     ColSet cs; NX_TRY(make_colset(ctx, d_cols, n_cols, &cs));
     return fft_interpolate(ctx, tw, cs, n_cols, log_size);
 }
@@ -592,6 +593,10 @@ int nx_evaluate_batch(nx_ctx* ctx, const nx_twiddles* tw, const uint32_t* const*
                       uint32_t log_expand, uint32_t* const* d_out) {
     NX_GUARD(ctx);
     if (n_cols == 0) return NX_OK;
+    if (log_size + log_expand >= 3) {      // an output of 2^1 / 2^2 rows: fft_tiny_kernel, words; a 2-word source is read word by word
+        if (log_size >= 2) NX_TRY(check_aligned(ctx, "nx_evaluate_batch", "d_polys", (const void* const*)d_polys, n_cols, 16));
+        NX_TRY(check_aligned(ctx, "nx_evaluate_batch", "d_out", (const void* const*)d_out, n_cols, 16));
+    }
     ColSet p, o;
     NX_TRY(make_colset(ctx, d_polys, n_cols, &p));
     NX_TRY(make_colset(ctx, d_out, n_cols, &o));

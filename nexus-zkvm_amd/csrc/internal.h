@@ -214,6 +214,12 @@ template <class T> static inline T* bias_rows(T* p, uint64_t row_begin) { return
 // Builds a ColSet from a host array of device pointers: constant stride is detected, otherwise the
 // table is staged into the context's device scratch ring (stream-ordered).
 int make_colset(nx_ctx* ctx, const uint32_t* const* h_ptrs, uint32_t n, ColSet* out);
+// The alignment contract of the entries whose kernels make 16- or 8-byte accesses on caller pointers with no word path (the memory
+// section of include/nexus_hip.h): NX_OK when every pointer of the host list is `align`-byte aligned (one OR over the pointers; NULL
+// entries pass), else NX_ERR_ARG "entry: arg[first_index + i] must be 16-byte aligned" for the first one that is not — before anything
+// is launched.  first_index < 0: a single pointer, named without an index.  The caller skips columns shorter than the access its
+// kernel makes (those sizes go through a word kernel).
+int check_aligned(nx_ctx* ctx, const char* entry, const char* arg, const void* const* h_ptrs, uint32_t n, uint32_t align, int64_t first_index = 0);
 // Stage arbitrary bytes into device scratch; returns device pointer (valid until the ring wraps).
 int stage(nx_ctx* ctx, const void* h_src, size_t bytes, void** d_out);
 int host_alloc(nx_ctx* ctx, size_t bytes, void** h_out);       // pinned host block owned by the caller until host_free (cached by size)

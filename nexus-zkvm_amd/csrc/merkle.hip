@@ -1075,6 +1075,8 @@ int nx_commit_root(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, 
         if (log_sizes[i] < 1 || log_sizes[i] > 29) return set_err(ctx, NX_ERR_ARG, "nx_commit_root: column log size outside 1 .. 29");
         max_log = std::max(max_log, log_sizes[i]);
     }
+    for (uint32_t i = 0; i < n_cols; i++)      // nx_lde_batch's rule, with this call's column index (log_blowup >= 1: an extension of >= 2^3 rows from 2^2)
+        if (log_sizes[i] >= 2) NX_TRY(check_aligned(ctx, "nx_commit_root", "d_cols", (const void* const*)(d_cols + i), 1, 16, i));
     if (log_blowup < 1 || max_log + log_blowup > 30) return set_err(ctx, NX_ERR_ARG, "nx_commit_root: log_blowup >= 1 and an extension of at most 2^30 rows required");
     const uint32_t el = max_log + log_blowup;
     const size_t M = (size_t)1 << el;
@@ -1153,6 +1155,7 @@ int nx_merkle_leaf_chain(nx_ctx* ctx, const uint32_t* const* d_cols, uint32_t n_
     if ((col_offset == 0) != (d_state_in == nullptr)) return set_err(ctx, NX_ERR_ARG, "nx_merkle_leaf_chain: d_state_in must be NULL exactly for the shard at column 0");
     if (log_size > 30 || row_begin + n_rows > ((uint64_t)1 << log_size)) return set_err(ctx, NX_ERR_ARG, "nx_merkle_leaf_chain: row range outside the column");
     if (n_rows == 0) return NX_OK;
+    { const void* p[2] = {d_state_in, d_state_out}; NX_TRY(check_aligned(ctx, "nx_merkle_leaf_chain", "d_state_in", p, 1, 16, -1)); NX_TRY(check_aligned(ctx, "nx_merkle_leaf_chain", "d_state_out", p + 1, 1, 16, -1)); }
     ColSet cs; NX_TRY(make_colset(ctx, d_cols, n_cols, &cs));
     return leaf_chain_launch(ctx, cs, n_cols, col_offset, total_cols, d_state_in, d_state_out, row_begin, n_rows);
 }

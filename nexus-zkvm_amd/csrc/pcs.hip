@@ -709,10 +709,19 @@ int accumulate_quotients_coeffs(nx_ctx* ctx, const nx_twiddles* tw, uint32_t log
 }  // namespace nx
 extern "C" {
 
+// quotient_kernel reads every column and writes every coordinate column four rows at a time; 2 rows go through quotient_small_kernel, words
+static int quotients_aligned(nx_ctx* ctx, const char* entry, uint32_t log_size, const uint32_t* const* d_cols, uint32_t n_cols, uint32_t* const* d_out4) {
+    if (log_size < 2) return NX_OK;
+    if (d_cols) NX_TRY(check_aligned(ctx, entry, "d_cols", (const void* const*)d_cols, n_cols, 16));
+    if (d_out4) NX_TRY(check_aligned(ctx, entry, "d_out4", (const void* const*)d_out4, 4, 16));
+    return NX_OK;
+}
+
 int nx_accumulate_quotients(nx_ctx* ctx, uint32_t log_size, const uint32_t* const* d_cols, uint32_t n_cols, const uint32_t random_coeff[4],
                             uint32_t n_batches, const uint32_t* points, const uint32_t* batch_counts, const uint32_t* col_idx,
                             const uint32_t* values, uint32_t* const* d_out4) {
     NX_GUARD(ctx);
+    NX_TRY(quotients_aligned(ctx, "nx_accumulate_quotients", log_size, d_cols, n_cols, d_out4));
     return accumulate_quotients_impl(ctx, log_size, d_cols, n_cols, random_coeff, n_batches, points, batch_counts, col_idx, values, nullptr, 1, d_out4, 0, (uint64_t)1 << log_size);
 }
 
@@ -720,6 +729,7 @@ int nx_accumulate_quotients_partial(nx_ctx* ctx, uint32_t log_size, const uint32
                                     uint32_t n_batches, const uint32_t* points, const uint32_t* batch_counts, const uint32_t* col_idx,
                                     const uint32_t* values, const uint8_t* entry_local, int include_line_terms, uint32_t* const* d_out4) {
     NX_GUARD(ctx);
+    NX_TRY(quotients_aligned(ctx, "nx_accumulate_quotients_partial", log_size, d_cols, n_cols, d_out4));
     return accumulate_quotients_impl(ctx, log_size, d_cols, n_cols, random_coeff, n_batches, points, batch_counts, col_idx, values, entry_local,
                                      include_line_terms, d_out4, 0, (uint64_t)1 << log_size);
 }
@@ -728,6 +738,7 @@ int nx_fold_circle_into_line(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const
                              const uint32_t alpha[4]) {
     NX_GUARD(ctx);
     if (src_log < 1 || (src_log >= 3 && src_log - 1 > tw->log_half)) return set_err(ctx, NX_ERR_ARG, "nx_fold_circle_into_line: bad log");
+    NX_TRY(check_aligned(ctx, "nx_fold_circle_into_line", "d_src4", (const void* const*)d_src4, 4, 8));      // a lane reads its pair of every coordinate as one 8-byte word
     Sec4 d; Sec4C s;
     for (int q = 0; q < 4; q++) { d.c[q] = d_dst4[q]; s.c[q] = d_src4[q]; }
     QM31 a = q_load(alpha);
@@ -742,6 +753,7 @@ int nx_fold_line(nx_ctx* ctx, const nx_twiddles* tw, const uint32_t* const* d_sr
     NX_GUARD(ctx);
     (void)n_doublings;  // half_odds(k).double() == half_odds(k-1): the domain of log size L is always half_odds(L)
     if (src_log < 1 || src_log > tw->log_half) return set_err(ctx, NX_ERR_ARG, "nx_fold_line: domain not covered by the twiddle tree");
+    NX_TRY(check_aligned(ctx, "nx_fold_line", "d_src4", (const void* const*)d_src4, 4, 8));      // a lane reads its pair of every coordinate as one 8-byte word
     Sec4 d; Sec4C s;
     for (int q = 0; q < 4; q++) { d.c[q] = d_dst4[q]; s.c[q] = d_src4[q]; }
     uint32_t n = 1u << (src_log - 1);

@@ -1787,6 +1787,10 @@ extern "C" {
 int nx_lde_batch(nx_ctx* ctx, const nx_twiddles* tw, uint32_t* const* d_cols, uint32_t n_cols, uint32_t log_size, uint32_t log_blowup,
                  uint32_t* const* d_lde) {
     NX_GUARD(ctx);
+    if (n_cols && d_cols && d_lde && log_size + log_blowup >= 3) {      // the rule of nx_interpolate_batch followed by nx_evaluate_batch
+        if (log_size >= 2) NX_TRY(nx::check_aligned(ctx, "nx_lde_batch", "d_cols", (const void* const*)d_cols, n_cols, 16));
+        NX_TRY(nx::check_aligned(ctx, "nx_lde_batch", "d_lde", (const void* const*)d_lde, n_cols, 16));
+    }
     return nxhip::lde_batch_from(ctx, tw, (const uint32_t* const*)d_cols, d_cols, n_cols, log_size, log_blowup, d_lde);   // in place
 }
 
