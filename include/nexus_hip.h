@@ -31,7 +31,7 @@
  *    d_states / d_states_out (8 bytes) and d_timestamps (16 bytes) themselves; their trace columns are written word by word.
  *    Entries whose host code chooses between a 16-byte and a word kernel by the pointers' low bits accept any word-aligned pointer and
  *    give the same words either way: nx_copy, nx_merkle_commit, nx_merkle_from_leaves, nx_upload_columns_narrow,
- *    nx_logup_multiplicities, nx_trace_prev_access, nx_trace_program.  Every other entry touches caller memory word by word.
+ *    nx_logup_multiplicities(_sparse), nx_trace_prev_access, nx_trace_program.  Every other entry touches caller memory word by word.
  *    tests/placement.py classifies every entry with the source lines; tests/test_gpu_placement.py runs each at every word offset.
  *  - Every function returns NX_OK (0) or a negative error code; nx_last_error() gives the text.
  *    Allocation failure is an error code, not a panic (reference: vec![] aborts, trace_builder.rs:29).
@@ -888,6 +888,40 @@ typedef struct nx_lookup_use {
 int nx_logup_multiplicities(nx_ctx* ctx, const nx_lookup_use* uses, uint32_t n_uses, uint32_t n_key_cols, const uint32_t* key_bits,
                             const uint32_t* const* d_table, uint32_t log_table, uint32_t* d_mult, uint64_t* n_missing,
                             uint32_t* first_missing_use, uint64_t* first_missing_pos);
+
+/* The same count for a table that is a SPARSE subset of a key space of up to 32 bits: the tables keyed by an address.  prover2's
+ * PrivateMemoryBoundary has one row per touched RAM address, with MultiplicityRead / MultiplicityWrite from the AddressAccessSideNote
+ * (prover2/machine/src/components/read_write_memory_boundary/private_memory/mod.rs:95-168, consumed at :249-262;
+ * read_write_memory/trace.rs:70-71,122,218); its Pub / Static / ProgramMemoryBoundary (keyed by pc) and v1's FinalPrgMemoryCtr are
+ * keyed the same way.  nx_logup_multiplicities would need a counter per key of the key space, 32 GiB for such a table; here the
+ * counters belong to the table's rows and a looked-up row finds its counter by a search.
+ * Everything is as in nx_logup_multiplicities — the uses (any row order, optional d_weight, at most 65536 uses, 2^30 rows per use,
+ * 2^32 rows in all), exact 64-bit sums reduced once mod p, the rule for missing rows and the text that names the first one,
+ * NX_ERR_PROTOCOL with d_mult still filled for the rows that are present, the same words on every run, blocking, every column at any
+ * word-aligned address — except:
+ * Key: 1 <= n_key_cols <= 4, 1 <= key_bits[i] <= 32, sum of key_bits <= 32; the packed key is that of nx_trace_prev_access.
+ * Table rows: d_table_valid is NULL (every row is a table row) or a column of 2^log_table words; a row is a table row iff its word is
+ * nonzero (the complement of IsPad).  The other rows may hold anything, copies of valid keys and values outside their bits included;
+ * d_mult gets 0 there, so every word of d_mult is written.  0 <= log_table <= 30.  A table without any valid row is legal: every row
+ * of nonzero weight is then missing.
+ * NX_ERR_ARG (nothing stays allocated, the context stays usable): the pointer and count refusals of nx_logup_multiplicities; d_mult
+ * equal to any input column pointer of the call; a valid table row with an entry >= 2^key_bits[i] ("table row position 5 holds a
+ * value outside its key_bits"); two valid table rows with one key — nx_last_error names the smallest position whose key also lies at
+ * a smaller valid position, that smallest position and the entries ("table row positions 3 and 9 hold the same key (7, 65535)").
+ * How: the valid rows become (key, position) pairs sorted by key (ceil(sum of key_bits / 8) stable counting passes); a row of a use
+ * finds its key by a binary search whose upper level — every 2^(log_table - NX_MULT_SPARSE_LDS_LOG_KEYS)-th sorted key — is staged
+ * in LDS; a table of up to 2^NX_MULT_SPARSE_LDS_LOG_KEYS rows is searched in LDS alone.
+ * DEVICE MEMORY: with T = 2^log_table and U = n_uses,
+ *     peak above the caller's columns  <=  16 T + 1024 min(256, ceil(T / 1024)) + 52 U + 4 * 2^NX_MULT_SPARSE_LDS_LOG_KEYS + 4096 bytes
+ * (two (key, position) buffers of 8 T each, of which the one the last sort pass has read then holds the 64-bit counters; the per-block
+ * digit counts of a pass; the use table; the splitters of a table the LDS does not hold whole) and NOTHING per key of the key space.  Taken from the context's allocator, released before
+ * the call returns. */
+#ifndef NX_MULT_SPARSE_LDS_LOG_KEYS
+#define NX_MULT_SPARSE_LDS_LOG_KEYS 12
+#endif
+int nx_logup_multiplicities_sparse(nx_ctx* ctx, const nx_lookup_use* uses, uint32_t n_uses, uint32_t n_key_cols, const uint32_t* key_bits,
+                                   const uint32_t* const* d_table, const uint32_t* d_table_valid, uint32_t log_table, uint32_t* d_mult,
+                                   uint64_t* n_missing, uint32_t* first_missing_use, uint64_t* first_missing_pos);
 
 /* ------------------------------------------- memory-checking columns: what the PREVIOUS access to the same address left behind ----
  * The reference fills these in one sequential pass over a map: Reg{1,2,3}TsPrev / ValPrev from RegisterMemCheckSideNote::access

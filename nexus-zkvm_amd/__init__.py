@@ -709,7 +709,8 @@ class TracePartition:
 
 
 MULT_LDS_MAX_KEY_BITS = 12   # NX_MULT_LDS_MAX_KEY_BITS: widest key space nx_logup_multiplicities counts in LDS
-KECCAK_ROUND_MAIN_COLS, KECCAK_ROUND_PRE_COLS = 1705, 9   # NX_KECCAK_ROUND_MAIN_COLS, NX_KECCAK_ROUND_PRE_COLS
+MULT_SPARSE_LDS_LOG_KEYS = 12   # NX_MULT_SPARSE_LDS_LOG_KEYS: largest table (log rows) nx_logup_multiplicities_sparse searches in LDS alone
+KECCAK_ROUND_MAIN_COLS, KECCAK_ROUND_PRE_COLS = 1705, 9  # NX_KECCAK_ROUND_MAIN_COLS, NX_KECCAK_ROUND_PRE_COLS
 KECCAK_MEMCHECK_MAIN_COLS, KECCAK_MEMCHECK_PRE_COLS = 2001, 1   # NX_KECCAK_MEMCHECK_MAIN_COLS, NX_KECCAK_MEMCHECK_PRE_COLS
 
 
@@ -1408,6 +1409,33 @@ class HipBackend:
         n, fu, fp = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
         rc = self.L.nx_logup_multiplicities(self.ctx, arr, len(uses), k, kb.ctypes.data_as(C.c_void_p), tp, int(log_table), C.c_void_p(int(out_ptr)),
                                             C.byref(n), C.byref(fu), C.byref(fp))
+        if rc not in (NX_OK, NX_ERR_PROTOCOL):
+            self._chk(rc)
+        res = (n.value, fu.value, fp.value)
+        return (res, rc) if want_rc else res
+
+    def logup_multiplicities_sparse(self, uses, table_ptrs, valid_ptr, log_table, key_bits, out_ptr, want_rc=False):
+        """logup_multiplicities for a table that is a sparse subset of a key space of up to 32 bits (nx_logup_multiplicities_sparse):
+        the boundary tables keyed by an address.  uses, table_ptrs, key_bits, out_ptr and the result are those of
+        logup_multiplicities; valid_ptr: None (every row is a table row) or the device pointer of 2^log_table words, a row being a
+        table row iff its word is nonzero.  out_ptr gets 0 on the other rows.  Temporaries follow the table's rows, not the key
+        space."""
+        kb = _u32(key_bits).reshape(-1)
+        k = len(kb)
+        if len(table_ptrs) != k:
+            raise NexusHipError(f"logup_multiplicities_sparse: {len(table_ptrs)} table columns for {k} key columns")
+        arr, keep = (LookupUse * max(1, len(uses)))(), []
+        for i, (vals, weight, log_size) in enumerate(uses):
+            if len(vals) != k:
+                raise NexusHipError(f"logup_multiplicities_sparse: use {i} has {len(vals)} value columns for {k} key columns")
+            vp = (C.c_void_p * k)(*[int(v) for v in vals])
+            keep.append(vp)
+            arr[i] = LookupUse(C.cast(vp, C.c_void_p), int(weight) if weight is not None else None, int(log_size))
+        tp = (C.c_void_p * max(1, k))(*[int(t) for t in table_ptrs])
+        n, fu, fp = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        rc = self.L.nx_logup_multiplicities_sparse(self.ctx, arr, len(uses), k, kb.ctypes.data_as(C.c_void_p), tp,
+                                                   C.c_void_p(int(valid_ptr)) if valid_ptr is not None else None, int(log_table),
+                                                   C.c_void_p(int(out_ptr)) if out_ptr is not None else None, C.byref(n), C.byref(fu), C.byref(fp))
         if rc not in (NX_OK, NX_ERR_PROTOCOL):
             self._chk(rc)
         res = (n.value, fu.value, fp.value)

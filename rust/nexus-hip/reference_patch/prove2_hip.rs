@@ -52,6 +52,36 @@ fn to_proving_error(e: HipError) -> ProvingError {
     }
 }
 
+/// The accesses of one RAM component as they lie on the device: the address limb columns, the numerator columns of its two relation
+/// entries (1 on a row that reads / writes, 0 elsewhere and on padding) and the component's log size.
+pub struct RamAccessColumns {
+    pub addr: Vec<*const u32>,
+    pub is_read: *const u32,
+    pub is_write: *const u32,
+    pub log_size: u32,
+}
+
+/// read_write_memory_boundary/private_memory/mod.rs:143-154 on the device: the boundary's MultiplicityRead and MultiplicityWrite columns,
+/// which `generate_component_trace` copies out of the `AddressAccessSideNote` (read_write_memory/trace.rs:70-71,122,218), counted from
+/// the accessing components' own columns instead (`nx_logup_multiplicities_sparse`, one call per relation: rel_ram_read_addr and
+/// rel_ram_write_addr, mod.rs:249-262).  The table is the boundary's address limbs, one row per touched address; `is_real` is the
+/// complement of its padding flag, so the padding rows get 0 as mod.rs:318-320 constrains.  `prove_hip` below still takes every main
+/// trace from the CPU, where the side note has the counts already; a host that fills the RAM components on the device
+/// (`Session::trace_prev_access` delivers the boundary's addresses and `is_real`) calls this for the two columns the side note would
+/// have given, and nothing of the memory argument is counted on the host.  An access to an address that is no boundary row is an error
+/// that names the component and the row.
+pub fn boundary_multiplicities_on_device(session: &mut Session, accesses: &[RamAccessColumns], addr_bits: &[u32], boundary_addr: &[*const u32], is_real: *const u32,
+                                         log_boundary: u32, mult_read: *mut u32, mult_write: *mut u32) -> Result<(), HipError> {
+    for (write, mult) in [(false, mult_read), (true, mult_write)] {
+        let uses: Vec<(&[*const u32], *const u32, u32)> = accesses.iter().map(|a| (a.addr.as_slice(), if write { a.is_write } else { a.is_read }, a.log_size)).collect();
+        let (n_missing, first) = session.logup_multiplicities_sparse(&uses, addr_bits, boundary_addr, is_real, log_boundary, mult)?;
+        if let Some((component, row)) = first {
+            return Err(HipError::Argument(format!("{n_missing} RAM accesses to addresses the boundary does not hold, the first in access component {component} at row position {row}")));
+        }
+    }
+    Ok(())
+}
+
 pub fn prove_hip(trace: &impl Trace, view: &View) -> Result<Proof, ProvingError> {
     // ---- prove.rs:35-42: component traces on the CPU, the reference's own statements
     let mut prover_side_note = SideNote::new(trace, view);

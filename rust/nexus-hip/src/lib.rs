@@ -439,6 +439,23 @@ impl Session {
             rc => try_check(self.ctx, rc).map(|_| (0, None)),
         }
     }
+    /// `logup_multiplicities` for a table that is a sparse subset of a key space of up to 32 bits (`nx_logup_multiplicities_sparse`):
+    /// the v2 boundary tables keyed by an address — PrivateMemoryBoundary's MultiplicityRead / MultiplicityWrite, which the reference
+    /// reads off the `AddressAccessSideNote` (prover2/machine/src/components/read_write_memory_boundary/private_memory/mod.rs:143-154) —
+    /// and v1's FinalPrgMemoryCtr.  `valid`: null (every row is a table row) or 2^log_table words, a row being a table row iff its
+    /// word is nonzero (the complement of IsPad); `mult` gets 0 on the other rows.  Everything else, the result included, is as in
+    /// `logup_multiplicities`; the temporaries follow the table's rows, never the key space.
+    pub fn logup_multiplicities_sparse(&mut self, uses: &[(&[*const u32], *const u32, u32)], key_bits: &[u32], table: &[*const u32], valid: *const u32, log_table: u32, mult: *mut u32)
+        -> Result<(u64, Option<(u32, u64)>), HipError> {
+        if table.len() != key_bits.len() || uses.iter().any(|u| u.0.len() != key_bits.len()) { return Err(HipError::Argument("logup_multiplicities_sparse: one column per key_bits entry".into())); }
+        let raw: Vec<sys::nx_lookup_use> = uses.iter().map(|u| sys::nx_lookup_use { d_values: u.0.as_ptr(), d_weight: u.1, log_size: u.2 }).collect();
+        let (mut n, mut first_use, mut first_pos) = (0u64, 0u32, 0u64);
+        match unsafe { sys::nx_logup_multiplicities_sparse(self.ctx, raw.as_ptr(), raw.len() as u32, key_bits.len() as u32, key_bits.as_ptr(), table.as_ptr(), valid, log_table, mult, &mut n, &mut first_use, &mut first_pos) } {
+            sys::NX_OK => Ok((0, None)),
+            sys::NX_ERR_PROTOCOL => Ok((n, Some((first_use, first_pos)))),
+            rc => try_check(self.ctx, rc).map(|_| (0, None)),
+        }
+    }
     /// The memory-checking columns filled on the device (`nx_trace_prev_access`): what the reference reads off
     /// `RegisterMemCheckSideNote::access` (prover/src/trace/regs.rs:29-37), `ReadWriteMemCheckSideNote::last_access`
     /// (prover/src/trace/sidenote/mod.rs:25-47) and `last_access_counter` (program_mem_check.rs:49-96) in one sequential pass.  `streams`
