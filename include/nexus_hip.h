@@ -989,7 +989,10 @@ int nx_trace_prev_access(nx_ctx* ctx, const nx_access_stream* streams, uint32_t 
  * A trace program is an nx_cinstr array over the BASE-FIELD register file: NX_C_LOAD (row offset taken in natural trace order, row
  * (i + o) mod 2^log_size, the rule of nx_air_check and nx_logup_program), NX_C_CONST, NX_C_ADD, NX_C_SUB, NX_C_MUL, NX_C_NEG and the
  * opcodes below.  Registers always hold canonical words: the 32-bit integer result r of an integer opcode is written as r mod p (only
- * OR, XOR and SHL can reach p), so there is no error path at run time. */
+ * OR, XOR and SHL can reach p), so there is no error path at run time.  A second register kind, W, holds a raw 32-bit integer
+ * (NX_T_PACK32 .. NX_T_REMU32): PACK32 makes one from two half-words, MULLO32 / MULHU32 / DIVU32 / REMU32 work on them with RISC-V's
+ * total division, LO16 / HI16 take the halves back into canonical words.  Signed MULH / DIV / REM need no opcode: the chips work on
+ * absolute values, signs and borrows, which the existing opcodes give. */
 enum {
     NX_T_STORE = 32,    /* cols[a][row] = B[b]                                   (dst must be 0)                       */
     NX_T_STORE_IF = 33, /* if (B[dst] != 0) cols[a][row] = B[b]; the column keeps its content elsewhere: several chips  */
@@ -999,7 +1002,17 @@ enum {
     NX_T_SHL = 38,      /* B[dst] = (B[a] << B[b]) truncated to 32 bits; a count >= 32 gives 0                          */
     NX_T_SHR = 39,      /* B[dst] = B[a] >> B[b]; a count >= 32 gives 0                                                 */
     NX_T_LTU = 40, NX_T_EQ = 41, /* B[dst] = 1 if B[a] < B[b] / B[a] == B[b] as integers, else 0                        */
-    NX_T_INV = 42       /* B[dst] = the M31 inverse of B[a]; the inverse of 0 is 0 (is-zero helper columns)             */
+    NX_T_INV = 42,      /* B[dst] = the M31 inverse of B[a]; the inverse of 0 is 0 (is-zero helper columns)             */
+    /* The W kind: one register holding a raw 32-bit integer that need not be canonical (the RV32M chips' 64-bit product bytes and
+     * quotients: prover/src/chips/instructions/m/).  A register has the kind its latest writer gave it; the program is straight-line,
+     * so the kind at every instruction is static.  Every opcode is a total function.                                              */
+    NX_T_PACK32 = 43,   /* W[dst] = (B[a] + (B[b] << 16)) truncated to 32 bits: a low and a high half-word                   */
+    NX_T_LO16 = 44,     /* B[dst] = W[a] & 0xFFFF                                  (b must be 0)                       */
+    NX_T_HI16 = 45,     /* B[dst] = W[a] >> 16                                     (b must be 0)                       */
+    NX_T_MULLO32 = 46,  /* W[dst] = the low 32 bits of W[a] * W[b]                                                      */
+    NX_T_MULHU32 = 47,  /* W[dst] = the high 32 bits of the unsigned 64-bit product W[a] * W[b]                         */
+    NX_T_DIVU32 = 48,   /* W[dst] = W[a] / W[b] unsigned; W[b] == 0 gives 0xFFFFFFFF (RISC-V DIVU)                      */
+    NX_T_REMU32 = 49    /* W[dst] = W[a] % W[b] unsigned; W[b] == 0 gives W[a]       (RISC-V REMU)                      */
 };
 /* Runs the program once per row and stores into d_cols, TRACE-DOMAIN EVALUATIONS in bit-reversed circle-domain order, 2^log_size
  * words each (1 <= log_size <= 30) — what nx_prover_tree_begin hands out before the commit; preprocessed, main and scratch columns
@@ -1009,7 +1022,9 @@ enum {
  * trace has at least four rows (context option "trace.vec4"; the same words either way).  A program too large for the instruction cache is cut at
  * store boundaries into kernels of at most "air.segment" estimated instructions, launched one after the other.
  * Refused with NX_ERR_ARG (nx_last_error names the instruction): a secure-field, constraint or fraction opcode; a program without a
- * store; a register read before an earlier instruction wrote it; a LOAD, at any offset, of a column that some store of the program
+ * store; a register read before an earlier instruction wrote it; a 32-bit integer opcode whose operand register is not W at that
+ * point; any other opcode (STORE and the STORE_IF flag included) reading a register that is W at that point; a nonzero b on LO16 /
+ * HI16; an opcode of 50 or more; a LOAD, at any offset, of a column that some store of the program
  * targets (lanes would race: chain two calls instead); a loaded or stored column whose pointer is NULL; an output column whose
  * pointer equals that of another entry of d_cols; a register out of range, a column index >= n_cols, an immediate >= p.
  * Stream-ordered like nx_air_eval: validation errors are returned at once, a later commit, check or download orders after the

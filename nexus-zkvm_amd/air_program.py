@@ -28,6 +28,10 @@ Derived trace columns are recorded the same way (nx_trace_program: the row-local
     pb.store(2, pb.band(s, 255)); pb.store(3, pb.shr(s, 8))       # ValueA byte and CarryFlag
     pb.store_if(flag, 4, pb.bxor(b, c))                           # only on the rows of this chip's flag
     prog = pb.build_trace_program()
+Raw 32-bit integers (the RV32M chips' products and quotients) are a kind of their own, "W": one register, no field arithmetic.
+    w = pb.pack32(lo, hi)                                         # two half-words
+    q, r = pb.divu32(w, d), pb.remu32(w, d)                       # RISC-V DIVU / REMU: total
+    pb.store(5, pb.lo16(pb.mullo32(q, d)))                        # back to canonical words by halves
 """
 import numpy as np
 
@@ -35,8 +39,11 @@ P = (1 << 31) - 1
 (LOAD, CONST, ADD, SUB, MUL, NEG, CONSTE, ADDE, SUBE, MULE, MULEB, ADDEB, LOADE, CONSTRAINT_B, CONSTRAINT_E, FRAC, FRACB) = range(17)
 # trace programs (nx_trace_program): NX_T_* of include/nexus_hip.h
 (T_STORE, T_STORE_IF, T_ROW, T_AND, T_OR, T_XOR, T_SHL, T_SHR, T_LTU, T_EQ, T_INV) = range(32, 43)
-_BIN = ("add", "sub", "mul", "adde", "sube", "mule", "muleb", "addeb", "band", "bor", "bxor", "shl", "shr", "ltu", "eq")
-_UN = ("neg", "inv")
+# the W kind: one register holding a raw 32-bit integer (the RV32M chips' products and quotients)
+(T_PACK32, T_LO16, T_HI16, T_MULLO32, T_MULHU32, T_DIVU32, T_REMU32) = range(43, 50)
+_BIN = ("add", "sub", "mul", "adde", "sube", "mule", "muleb", "addeb", "band", "bor", "bxor", "shl", "shr", "ltu", "eq",
+        "pack32", "mullo32", "mulhu32", "divu32", "remu32")
+_UN = ("neg", "inv", "lo16", "hi16")
 
 
 class Expr:
@@ -46,6 +53,8 @@ class Expr:
         self.pb, self.id, self.kind = pb, nid, kind
 
     def _lift(self, o):
+        if self.kind == "W" or (isinstance(o, Expr) and o.kind == "W"):
+            raise TypeError("a 32-bit integer value has no field arithmetic: take lo16 / hi16 of it")
         if isinstance(o, Expr):
             return o
         return self.pb.const(int(o))
@@ -65,6 +74,7 @@ class Expr:
     __rmul__ = __mul__
 
     def __neg__(self):
+        self._lift(0)
         return self.pb._neg(self)
 
 
@@ -220,6 +230,43 @@ class ProgramBuilder:
         """The M31 inverse; inv(0) = 0"""
         return self._node(("inv", self._b(x).id), "B")
 
+    # ---- the W kind: raw 32-bit integers (NX_T_PACK32 .. NX_T_REMU32)
+    def _w(self, x):
+        assert isinstance(x, Expr) and x.kind == "W", "a 32-bit integer value is needed: pack32 makes one"
+        return x
+
+    def _w2(self, op, x, y, commutative=False):
+        x, y = self._w(x), self._w(y)
+        if commutative and y.id < x.id:
+            x, y = y, x
+        return self._node((op, x.id, y.id), "W")
+
+    def pack32(self, lo, hi):
+        """(lo + (hi << 16)) truncated to 32 bits: a 32-bit integer from a low and a high half-word"""
+        return self._node(("pack32", self._b(lo).id, self._b(hi).id), "W")
+
+    def lo16(self, w):
+        return self._node(("lo16", self._w(w).id), "B")
+
+    def hi16(self, w):
+        return self._node(("hi16", self._w(w).id), "B")
+
+    def mullo32(self, x, y):
+        """the low 32 bits of the product"""
+        return self._w2("mullo32", x, y, True)
+
+    def mulhu32(self, x, y):
+        """the high 32 bits of the unsigned 64-bit product"""
+        return self._w2("mulhu32", x, y, True)
+
+    def divu32(self, x, y):
+        """x / y unsigned; y == 0 gives 0xFFFFFFFF (RISC-V DIVU)"""
+        return self._w2("divu32", x, y)
+
+    def remu32(self, x, y):
+        """x % y unsigned; y == 0 gives x (RISC-V REMU)"""
+        return self._w2("remu32", x, y)
+
     def store(self, col, value):
         """cols[col][row] = value"""
         self.stores.append((int(col), self._b(value).id, None))
@@ -373,7 +420,7 @@ class ProgramBuilder:
         alloc_log = []
         for pos, (what, i) in enumerate(order):
             if what == "node":
-                if nodes[i][1] == "B":
+                if nodes[i][1] != "E":                       # a W value takes one register, as a base-field value does
                     if free_b:
                         slot[i] = ("B", free_b.pop())
                     else:
@@ -409,7 +456,8 @@ class ProgramBuilder:
 
         out = []
         opmap = {"add": ADD, "sub": SUB, "mul": MUL, "adde": ADDE, "sube": SUBE, "mule": MULE, "muleb": MULEB, "addeb": ADDEB,
-                 "band": T_AND, "bor": T_OR, "bxor": T_XOR, "shl": T_SHL, "shr": T_SHR, "ltu": T_LTU, "eq": T_EQ}
+                 "band": T_AND, "bor": T_OR, "bxor": T_XOR, "shl": T_SHL, "shr": T_SHR, "ltu": T_LTU, "eq": T_EQ,
+                 "pack32": T_PACK32, "mullo32": T_MULLO32, "mulhu32": T_MULHU32, "divu32": T_DIVU32, "remu32": T_REMU32}
         for what, i in order:
             if what == "cons":
                 out.append((CONSTRAINT_B if nodes[i][1] == "B" else CONSTRAINT_E, 0, reg(i), 0))
@@ -435,6 +483,8 @@ class ProgramBuilder:
                 out.append((NEG, reg(i), reg(key[1]), 0))
             elif key[0] == "inv":
                 out.append((T_INV, reg(i), reg(key[1]), 0))
+            elif key[0] in ("lo16", "hi16"):
+                out.append((T_LO16 if key[0] == "lo16" else T_HI16, reg(i), reg(key[1]), 0))
             elif key[0] == "row":
                 out.append((T_ROW, reg(i), 0, 0))
             else:

@@ -2,6 +2,7 @@
 #pragma once
 #include <vector>
 #include "internal.h"
+#include "trace_w.h"      // the 32-bit integer register kind of trace programs
 
 namespace nx {
 

@@ -145,7 +145,7 @@ static uint32_t instr_cost(uint32_t op) {   // rough gfx950 instruction counts o
     // trace programs (nx_trace_program): INV is the 37-product exponentiation chain
     case NX_T_STORE: return 3; case NX_T_STORE_IF: return 5; case NX_T_ROW: return 1; case NX_T_AND: case NX_T_SHR: case NX_T_LTU: case NX_T_EQ: return 2;
     case NX_T_OR: case NX_T_XOR: return 5; case NX_T_SHL: return 7; case NX_T_INV: return 260;
-    default: return 1;
+    default: return is_w_opcode(op) ? w_instr_cost(op) : 1;       // the 32-bit integer register kind: trace_w.h
     }
 }
 // estimated-instruction budget of one generated kernel: ~70 KB of code per kernel at the default 9000; measured sweep 1500..60000
@@ -181,7 +181,7 @@ static void instr_ranges(const nx_cinstr& in, std::vector<RegRange>* reads, RegR
     case NX_T_ROW: *write = {in.dst, 1}; break;
     case NX_T_AND: case NX_T_OR: case NX_T_XOR: case NX_T_SHL: case NX_T_SHR: case NX_T_LTU: case NX_T_EQ: reads->push_back({in.a, 1}); reads->push_back({in.b, 1}); *write = {in.dst, 1}; break;
     case NX_T_INV: reads->push_back({in.a, 1}); *write = {in.dst, 1}; break;
-    default: break;
+    default: if (is_w_opcode(in.op)) { reads->push_back({in.a, 1}); if (!w_opcode_is_unary(in.op)) reads->push_back({in.b, 1}); *write = {in.dst, 1}; } break;
     }
 }
 struct DotFusion { std::vector<char> skip, fused; };      // by position in `keep`: the MULEB that is not emitted, the ADDE that becomes 4 multiply-adds
@@ -380,7 +380,7 @@ static ProgDeps program_deps(const nx_cinstr* prog, uint32_t n_instr, uint32_t n
         case NX_T_ROW: def(i, in.dst, 1); break;
         case NX_T_AND: case NX_T_OR: case NX_T_XOR: case NX_T_SHL: case NX_T_SHR: case NX_T_LTU: case NX_T_EQ: use(i, in.a, 1); use(i, in.b, 1); def(i, in.dst, 1); break;
         case NX_T_INV: use(i, in.a, 1); def(i, in.dst, 1); break;
-        default: break;
+        default: if (is_w_opcode(in.op)) { use(i, in.a, 1); if (!w_opcode_is_unary(in.op)) use(i, in.b, 1); def(i, in.dst, 1); } break;
         }
     }
     return pd;
@@ -1442,7 +1442,7 @@ static bool trace_vec4_wanted(const nx_ctx* ctx) {      // per context ("trace.v
 int validate_trace_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_instr, uint32_t n_regs, uint32_t n_cols) {
     if (!program) return set_err(ctx, NX_ERR_ARG, "trace program: NULL program");
     if (n_regs == 0 || n_regs > 4096) return set_err(ctx, NX_ERR_ARG, "trace program: register count out of range");
-    std::vector<char> written(n_regs, 0), stored(n_cols, 0);
+    std::vector<char> written(n_regs, 0), is_w(n_regs, 0), stored(n_cols, 0);      // is_w: the kind the register's latest writer gave it (trace_w.h)
     bool any_store = false;
     auto bad = [&](uint32_t i, const char* why) { return set_err(ctx, NX_ERR_ARG, std::string("trace program: instruction ") + std::to_string(i) + ": " + why); };
     std::vector<RegRange> reads; RegRange wr;
@@ -1452,7 +1452,7 @@ int validate_trace_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_ins
         case NX_C_LOAD: if (in.a >= n_cols) return bad(i, "column index beyond the column table"); break;
         case NX_C_CONST: if (in.a >= P) return bad(i, "immediate not below p"); break;
         case NX_C_ADD: case NX_C_SUB: case NX_C_MUL: case NX_C_NEG: case NX_T_ROW: case NX_T_AND: case NX_T_OR: case NX_T_XOR: case NX_T_SHL: case NX_T_SHR: case NX_T_LTU: case NX_T_EQ:
-        case NX_T_INV: break;
+        case NX_T_INV: break; case NX_T_PACK32: case NX_T_MULLO32: case NX_T_MULHU32: case NX_T_DIVU32: case NX_T_REMU32: break; case NX_T_LO16: case NX_T_HI16: if (in.b != 0) return bad(i, "b of a LO16 / HI16 must be 0"); break;
         case NX_T_STORE: if (in.dst != 0) return bad(i, "dst of a STORE must be 0");
             [[fallthrough]];
         case NX_T_STORE_IF: if (in.a >= n_cols) return bad(i, "column index beyond the column table"); stored[in.a] = 1; any_store = true; break;
@@ -1464,9 +1464,9 @@ int validate_trace_program(nx_ctx* ctx, const nx_cinstr* program, uint32_t n_ins
         instr_ranges(in, &reads, &wr);
         for (const RegRange& r : reads) {
             if (r.reg >= n_regs) return bad(i, "register out of range");
-            if (!written[r.reg]) return bad(i, "reads a register no earlier instruction wrote");
+            if (!written[r.reg]) return bad(i, "reads a register no earlier instruction wrote");   if (const char* why = w_kind_error(in.op, is_w[r.reg] != 0)) return bad(i, why);
         }
-        if (wr.w) { if (wr.reg >= n_regs) return bad(i, "register out of range"); written[wr.reg] = 1; }
+        if (wr.w) { if (wr.reg >= n_regs) return bad(i, "register out of range"); written[wr.reg] = 1; is_w[wr.reg] = w_opcode_writes_w(in.op); }
     }
     if (!any_store) return set_err(ctx, NX_ERR_ARG, "trace program: no STORE / STORE_IF instruction (nothing would be written)");
     for (uint32_t i = 0; i < n_instr; i++)
@@ -1533,7 +1533,7 @@ static std::string generate_trace_kernel(const nx_cinstr* prog, const std::vecto
             case NX_T_INV: s += "  " + R(in.dst) + " = m_inv(" + R(in.a) + ");\n"; break;
             case NX_T_STORE: s += (vec4 ? "  o" + std::to_string(in.a) + J : "  GW(cols[" + std::to_string(in.a) + "])[r]") + " = " + R(in.b) + ";\n"; break;
             case NX_T_STORE_IF: s += "  if (" + R(in.dst) + ") " + (vec4 ? "o" + std::to_string(in.a) + J : "GW(cols[" + std::to_string(in.a) + "])[r]") + " = " + R(in.b) + ";\n"; break;
-            default: break;
+            default: s += trace_w_statement(in); break;        // the 32-bit integer opcodes (nothing for any other: the program is validated)
             }
         }
         if (vec4) s += "  }\n";
@@ -1544,7 +1544,7 @@ static std::string generate_trace_kernel(const nx_cinstr* prog, const std::vecto
 
 static std::string generate_trace_source(const nx_ctx* ctx, const nx_cinstr* prog, uint32_t n_instr, uint32_t n_regs, uint32_t* n_kernels, bool vec4) {
     const ProgDeps pd = program_deps(prog, n_instr, n_regs);
-    std::string s = std::string(AIR_PRELUDE) + TRACE_ROWS_PRELUDE + M_INV_PRELUDE + TRACE_PRELUDE;
+    std::string s = std::string(AIR_PRELUDE) + TRACE_ROWS_PRELUDE + M_INV_PRELUDE + TRACE_PRELUDE + (uses_w_opcodes(prog, n_instr) ? TRACE_W_PRELUDE : "");
     uint32_t n_seg = 0, cost = 0;
     std::vector<char> in_seg(n_instr, 0);
     auto add_slice = [&](uint32_t root) {

@@ -60,6 +60,18 @@ impl TraceProgram {
     pub fn eq(&mut self, x: Reg, y: Reg) -> Reg { self.push(sys::NX_T_EQ, x.0, y.0) }
     /// the M31 inverse; the inverse of 0 is 0 (is-zero helper columns)
     pub fn inv(&mut self, x: Reg) -> Reg { self.push(sys::NX_T_INV, x.0, 0) }
+    /// a 32-bit integer register (the W kind) from a low and a high half-word: `(lo + (hi << 16))` truncated to 32 bits.  The five
+    /// opcodes below work on such registers only; a field opcode or a store that reads one is refused
+    pub fn pack32(&mut self, lo: Reg, hi: Reg) -> Reg { self.push(sys::NX_T_PACK32, lo.0, hi.0) }
+    /// the low / high half-word of a 32-bit integer register, a canonical word again
+    pub fn lo16(&mut self, w: Reg) -> Reg { self.push(sys::NX_T_LO16, w.0, 0) }
+    pub fn hi16(&mut self, w: Reg) -> Reg { self.push(sys::NX_T_HI16, w.0, 0) }
+    /// the low / high 32 bits of the unsigned 64-bit product
+    pub fn mullo32(&mut self, x: Reg, y: Reg) -> Reg { self.push(sys::NX_T_MULLO32, x.0, y.0) }
+    pub fn mulhu32(&mut self, x: Reg, y: Reg) -> Reg { self.push(sys::NX_T_MULHU32, x.0, y.0) }
+    /// RISC-V DIVU / REMU: a zero divisor gives 0xFFFF_FFFF / the dividend
+    pub fn divu32(&mut self, x: Reg, y: Reg) -> Reg { self.push(sys::NX_T_DIVU32, x.0, y.0) }
+    pub fn remu32(&mut self, x: Reg, y: Reg) -> Reg { self.push(sys::NX_T_REMU32, x.0, y.0) }
     /// `cols[col][row] = value`
     pub fn store(&mut self, col: u32, value: Reg) {
         self.instrs.push(sys::nx_cinstr { op: sys::NX_T_STORE, dst: 0, a: col, b: value.0 });
