@@ -1347,12 +1347,16 @@ int prepare_component_kernels(nx_ctx* ctx, const PcsConfig& cfg, GComponent& g, 
     std::vector<int> where_c(g.n_constraints);
     for (uint32_t j = 0; j < g.n_constraints; j++) where_c[j] = where_of[deg[j] <= 2 ? 0 : deg[j] == 3 ? 1 : 2];
     if (can_quarter) {
-        // degree 4 / 5 (d <= 2^2 + 1: the quotient has 3N + 1 coefficients)
+        // degree 4 only: its quotient has 3N + 1 coefficients, which is what 3N + 1 samples determine.  A degree-5 quotient has 4N
+        // (d <= 2^2 + 1 is the bound for FITTING the 4N-point space, not for this shortcut): it stays on the component's own domain
+        // (tests/test_exact_algebra_cpu.py::test_degree_five_fills_the_4n_space_and_degree_six_overflows_it).  The degree is the
+        // estimate of air_constraint_degrees, an upper bound: a constraint estimated at 5 whose true degree is 4 (a factor that is
+        // a constant column) goes to the full domain too — slower, but right wherever the estimate errs.
         std::vector<char> nb;
         air_constraint_neighbours(g.prog.data(), (uint32_t)g.prog.size(), g.n_regs, &nb);
         // "air.quarter_domain" = 2 (the default): neighbour-reading constraints too — their columns get a 2N-point transform (compute_composition)
         const bool with_neighbours = ctx->opt.air_quarter_domain >= 2;
-        for (uint32_t j = 0; j < g.n_constraints; j++) if (where_c[j] == GComponent::ON_FULL && deg[j] >= 4 && deg[j] <= 5 && (with_neighbours || !nb[j])) where_c[j] = GComponent::ON_QUARTER;
+        for (uint32_t j = 0; j < g.n_constraints; j++) if (where_c[j] == GComponent::ON_FULL && deg[j] == 4 && (with_neighbours || !nb[j])) where_c[j] = GComponent::ON_QUARTER;
     }
     std::vector<GComponent::Part> parts;
     for (int where : {GComponent::ON_HALF, GComponent::ON_LOW, GComponent::ON_QUARTER, GComponent::ON_FULL}) {
@@ -1437,8 +1441,8 @@ static int axpy_scale(nx_ctx* ctx, u32* out, const u32* a, const u32* b, u32 s1,
 }
 
 // The same decomposition one level up (tests/test_exact_algebra_cpu.py::
-// test_degree_four_quotient_from_3n_plus_1_samples states it on the oracle).  The quotient F of constraints of degree 4 / 5 over columns
-// of N rows lives in the 4N-point space with 3N + 1 coefficients:  F = F0 + Z2 (F10 + t Z),  F0 in the 2N-point space, Z2 the vanishing
+// test_degree_four_quotient_from_3n_plus_1_samples states it on the oracle).  The quotient F of constraints of degree 4 over columns
+// of N rows lives in the 4N-point space with 3N + 1 coefficients (degree 5 fills all 4N and is not taken here):  F = F0 + Z2 (F10 + t Z),  F0 in the 2N-point space, Z2 the vanishing
 // polynomial of the committed 2N-point domain, F10 in the N-point space, Z the trace domain's vanishing polynomial, t a secure scalar.
 //  * Z2 = 0 on the committed domain: evaluating the constraints on the COMMITTED 2N rows (no extension at all) and interpolating gives F0;
 //  * the first QUARTER of the bit-reversed 4N-point domain is an N-point circle domain (twiddles_first_part, depth 2) on which Z2 and Z
@@ -1501,7 +1505,7 @@ int GenericAir::compute_composition(CommitmentSchemeProver& cs, QM31 random_coef
     { QM31 a = q_one(); for (size_t i = 0; i < total; i++) { powers[i] = a; a = q_mul(a, random_coeff); } }
     std::map<uint32_t, SecureColumn> sub;
     std::map<uint32_t, HalfGroup> halves;                                     // by log_size: the half-domain parts of all components of that size
-    std::map<uint32_t, QuarterGroup> quarters;                                // by log_size: the quarter-domain parts (degree 4 / 5) of all components of that size
+    std::map<uint32_t, QuarterGroup> quarters;                                // by log_size: the quarter-domain parts (degree 4) of all components of that size
     std::map<uint32_t, nx_twiddles*> qtw;                                     // quarter-domain twiddles by log_size
     struct QtwGuard { std::map<uint32_t, nx_twiddles*>& m; ~QtwGuard() { for (auto& kv : m) nx_twiddles_destroy(kv.second); } } qtw_guard{qtw};
     size_t remaining = total;

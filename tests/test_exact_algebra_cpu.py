@@ -7,6 +7,8 @@ rest on, with the oracle's own transforms:
     tables' layers (what fft.hip twiddles_first_half builds);
   * the quotient of a degree-2 constraint is Q0 + t Z: one coefficient beyond the N-point space, at index N;
   * t follows from the first half and ONE further row; a degree-3 quotient fills the 2N-point space, a degree-4 one does not fit it;
+  * a degree-4 quotient is f0 + Z2 (f10 + t Z), 3N + 1 coefficients from 3N + 1 samples; a degree-5 one fills the 4N-point space, so
+    that assembly is not it; a degree-6 one does not fit 4N points;
   * a linear combination of columns can be taken in coefficient space (the DEEP-quotient numerators)."""
 import numpy as np
 import pytest
@@ -135,8 +137,44 @@ def test_linear_combinations_commute_with_extension(oracle):
         assert np.array_equal(np.array(rows, np.uint32), T.evaluate(np.array(comb, np.uint32), n + 1))
 
 
+def _quotient_rows(T, n, cols, cc, e, rows):
+    """rows of Q = (f_1 ... f_d - c) / Z on the 2^(n+e)-point domain"""
+    den = denominators(n, n + e)
+    ev = [T.evaluate(c, n + e) for c in cols]
+    Cc = T.evaluate(cc, n + e)
+    out = []
+    for r in rows:
+        p = 1
+        for v in ev:
+            p = p * int(v[r]) % P
+        out.append((p - int(Cc[r])) % P * int(den[r >> n]) % P)
+    return out
+
+
+def _from_3n_plus_1_samples(T, itw, n, cols, cc):
+    """(the 4N coefficients f0 | f10 | t, 0 ... assembled from the committed 2N rows, the first quarter of the 4N-point domain and row N;
+    the 4N coefficients of the plain interpolation of all 4N rows)"""
+    N = 1 << n
+    inv = lambda x: pow(int(x) % P, P - 2, P)
+    full = [int(x) for x in T.interpolate(np.array(_quotient_rows(T, n, cols, cc, 2, range(4 * N)), np.uint32))]      # Stwo's way: all 4N rows
+    # 1. the committed 2N rows -> f0
+    f0 = T.interpolate(np.array(_quotient_rows(T, n, cols, cc, 1, range(2 * N)), np.uint32))
+    # 2. N rows of the first quarter + row N
+    f0_4n = T.evaluate(f0, n + 2)
+    z2 = inv(denominators(n + 1, n + 2)[0])                       # Z2 = vanishing polynomial of the committed domain: constant on the first half
+    d4 = denominators(n, n + 2)
+    z0, z1 = inv(d4[0]), inv(d4[1])                               # Z on the first and the second quarter
+    fq = _quotient_rows(T, n, cols, cc, 2, range(N + 1))
+    g = [(fq[r] - int(f0_4n[r])) % P * inv(z2) % P for r in range(N + 1)]
+    I = sub_interpolate(g[:N], n, n + 2, itw)
+    Iw = int(T.evaluate(np.array(I, np.uint32), n + 2)[N])
+    t = (g[N] - Iw) * inv(z1 - z0) % P
+    I[0] = (I[0] - t * z0) % P
+    return [int(x) for x in f0] + I + [t] + [0] * (N - 1), full
+
+
 def test_degree_four_quotient_from_3n_plus_1_samples(oracle):
-    """The next lever (not built in the product): f = f0 + Z2 (f10 + t Z) for a degree-4 quotient — f0 from the
+    """The quarter-domain composition: f = f0 + Z2 (f10 + t Z) for a degree-4 quotient — f0 from the
     committed 2N rows, f10 from the first QUARTER of the 4N-point domain (itself an N-point domain: the first quarters of the 4N tables'
     layers), t from one further row; 3N + 1 constraint evaluations instead of 4N, and an N-point transform per column instead of a 4N one."""
     n, rng = 5, np.random.default_rng(9)
@@ -144,40 +182,45 @@ def test_degree_four_quotient_from_3n_plus_1_samples(oracle):
     T = O.Twiddles(n + 2)
     _, itw = _tables(T)
     cols, cc = _vanishing_product_quotient(T, n, 4, rng)
-    inv = lambda x: pow(int(x) % P, P - 2, P)
-
-    def quotient_rows(e, rows):
-        den = denominators(n, n + e)
-        ev = [T.evaluate(c, n + e) for c in cols]
-        Cc = T.evaluate(cc, n + e)
-        out = []
-        for r in rows:
-            p = 1
-            for v in ev:
-                p = p * int(v[r]) % P
-            out.append((p - int(Cc[r])) % P * int(den[r >> n]) % P)
-        return out
-    full = [int(x) for x in T.interpolate(np.array(quotient_rows(2, range(4 * N)), np.uint32))]      # Stwo's way: all 4N rows
     # the first quarter of the 4N-point domain is an N-point domain (first quarters of the layers)
     assert sub_interpolate(T.evaluate(cols[0], n + 2)[:N], n, n + 2, itw) == [int(x) for x in cols[0]]
-    # 1. the committed 2N rows -> f0
-    f0 = T.interpolate(np.array(quotient_rows(1, range(2 * N)), np.uint32))
-    # 2. N rows of the first quarter + row N
-    f0_4n = T.evaluate(f0, n + 2)
-    z2 = inv(denominators(n + 1, n + 2)[0])                       # Z2 = vanishing polynomial of the committed domain: constant on the first half
-    d4 = denominators(n, n + 2)
-    z0, z1 = inv(d4[0]), inv(d4[1])                               # Z on the first and the second quarter
-    fq = quotient_rows(2, range(N + 1))
-    g = [(fq[r] - int(f0_4n[r])) % P * inv(z2) % P for r in range(N + 1)]
-    I = sub_interpolate(g[:N], n, n + 2, itw)
-    Iw = int(T.evaluate(np.array(I, np.uint32), n + 2)[N])
-    t = (g[N] - Iw) * inv(z1 - z0) % P
-    I[0] = (I[0] - t * z0) % P
-    assert [int(x) for x in f0] + I + [t] + [0] * (N - 1) == full
+    assembled, full = _from_3n_plus_1_samples(T, itw, n, cols, cc)
+    assert assembled == full
+
+
+def test_degree_five_fills_the_4n_space_and_degree_six_overflows_it(oracle):
+    """d <= 2^2 + 1 is the bound for FITTING the 4N-point space, not for the 3N + 1-sample shortcut: the quotient of a degree-d constraint
+    has (d - 1) N + 1 coefficients.  A quintic quotient has non-zero coefficients at every index 3N + 1 .. 4N - 1, so f0 + Z2 (f10 + t Z)
+    assembled from 3N + 1 samples is NOT it — the quarter domain stops at degree 4, as the half domain stops at degree 2.  A sextic
+    quotient does not fit 4N points at all (what a log_constraint_degree_bound of 2 cannot hold)."""
+    n, rng = 5, np.random.default_rng(13)
+    N = 1 << n
+    T = O.Twiddles(n + 3)
+    _, itw = _tables(O.Twiddles(n + 2))
+    last = lambda co: max(i for i, x in enumerate(co) if x)
+    on = lambda cols, cc, e: [int(x) for x in T.interpolate(np.array(_quotient_rows(T, n, cols, cc, e, range(N << e)), np.uint32))]
+    # degree 4, the control: 3N + 1 coefficients on either domain
+    cols, cc = _vanishing_product_quotient(T, n, 4, rng)
+    q4, q8 = on(cols, cc, 2), on(cols, cc, 3)
+    assert last(q4) == 3 * N and q8 == q4 + [0] * (4 * N)
+    # degree 5: fits 4N points, and fills them
+    cols, cc = _vanishing_product_quotient(T, n, 5, rng)
+    q4, q8 = on(cols, cc, 2), on(cols, cc, 3)
+    assert q8 == q4 + [0] * (4 * N)                                              # fits: the 8N-point interpolation adds nothing
+    assert last(q4) == 4 * N - 1 and all(q4[3 * N + 1:4 * N])                    # all 31 coefficients beyond 3N + 1 are non-zero
+    assembled, full = _from_3n_plus_1_samples(O.Twiddles(n + 2), itw, n, cols, cc)
+    assert full == q4 and assembled != full                                      # the shortcut's polynomial is another one ...
+    assert not any(assembled[3 * N + 1:]) and assembled[:2 * N] == full[:2 * N]  # ... of 3N + 1 coefficients: f0 is right (Z2 = 0 on the committed rows),
+    assert assembled[2 * N:3 * N] != full[2 * N:3 * N]                           # (f - f0) / Z2 has 2N coefficients and aliases on the quarter's N points
+    # degree 6: 5N + 1 coefficients, aliased on 4N points
+    cols, cc = _vanishing_product_quotient(T, n, 6, rng)
+    q4, q8 = on(cols, cc, 2), on(cols, cc, 3)
+    assert last(q8) == 5 * N and all(q8[4 * N:5 * N - 1])                       # coefficients up to index 5N beyond the 4N-point space ...
+    assert q8[:4 * N] == q4                                                      # ... which the 4N-point interpolation drops (their basis functions vanish there)
 
 
 def test_neighbour_rows_of_the_first_quarter_are_the_second_quarter(oracle):
-    """The next lever of the quarter-domain composition: a constraint of degree 4 / 5 that reads a neighbour row
+    """The next lever of the quarter-domain composition: a constraint of degree 4 that reads a neighbour row
     (mask offset +-1) is kept on the 4N-point domain today.  The first quarter of the bit-reversed 4N-point domain is +-(g + <g_{N/2}>)
     with g of order 8N; the trace step has order N, and g + g_N lands in the coset whose bit-reversed positions are the SECOND quarter
     (index bits 10 below the top), an even multiple of the step back in the first.  So the neighbour reads of the quarter-domain rows

@@ -346,7 +346,7 @@ def _run_ranks_collect(nz, world, make_impl, fn, timeout=120):
 
 def test_quarter_domain_inside_a_row_sharded_proof_sends_a_quarter_of_the_rows(be, nz):
     """Round 6 (VERDICT r5 missing #4 / next #5): "air.quarter_domain" is no longer switched off by a communicator.  A +2 component's
-    degree-4 / 5 constraints take their columns on the first quarter of the 4N-point domain from an N-point transform on each column's
+    degree-4 constraints take their columns on the first quarter of the 4N-point domain from an N-point transform on each column's
     OWNER and an all-to-all of N / W rows (a handful of neighbour-read columns: 2N points, all-gathered whole), row N from sweeps on the
     owners and a host all-gather, the committed 2N rows as the row blocks they already are; the accumulators are gathered and the
     coefficient assembly is replicated.  Same bytes as one GPU with the option on or off on 2, 4 and 8 ranks — and the rank sends LESS
