@@ -981,6 +981,71 @@ int nx_trace_prev_access(nx_ctx* ctx, const nx_access_stream* streams, uint32_t 
                          const uint32_t* key_bits, uint32_t n_payload, const uint32_t* init, const nx_access_summary* summary,
                          uint64_t* n_keys);
 
+/* ------------------------------------------- memory-checking columns when an access leaves behind what depends on what it FOUND ---
+ * nx_trace_prev_access needs every access to know in advance what it leaves.  The load/store chip does (last_access.insert(addr,
+ * (clk, value)), prover/src/chips/instructions/i/load_store.rs:199-205); the keccak chip does not: KeccakChip::update_state_timestamps
+ * (prover/src/chips/custom.rs:107-123) touches the 200 bytes at addr + i, reports the timestamp it finds and leaves ts + 1 with the
+ * output byte, so two calls on one buffer chain through each other and every later load or store of those bytes reads the chained
+ * value as Ram*TsPrev.  This entry is nx_trace_prev_access with two additions: payload columns may CHAIN, and a stream may be a list
+ * of BLOCK records.  It is the stage between nx_trace_keccak_round (whose d_states_out it reads as bytes) and
+ * nx_trace_keccak_memory_check (whose d_timestamps it writes).
+ * A COLUMN stream (d_row == NULL) is an nx_access_stream: one access per position of 2^log_size; its natural row is the coset-order
+ * row of the position, or the position itself when linear != 0.  A BLOCK stream (d_row != NULL) is a list of n_records records, the
+ * keccak instances: record j makes `span` accesses at natural row d_row[j], sub-access i to the packed key key(j) + i, where key(j) is
+ * packed from d_key[k][j].  d_key[k], d_flag and d_row hold one word per record; every per-access array of a block stream is
+ * record-major, element j * span + i: d_payload[c] of a GIVEN column one word per element, or with NX_CHAIN_BYTES byte i of a record of
+ * `span` bytes (records contiguous, the array 4-byte aligned, span % 4 == 0: the layout of d_states_out); d_prev[c] and d_ordinal one
+ * word per element (the layout nx_trace_keccak_memory_check reads as d_timestamps).  log_size is ignored for a block stream, n_records
+ * and span for a column stream.  At most 8 block streams per call; 1 <= span <= 256; n_records may be 0.
+ * TIME ORDER (total): lexicographic in (epoch, natural row, index of the stream in `streams`, sub-access i).
+ * CHAINING: walk the accesses to one key in time order with a state of n_payload words that starts at init.  An access gets the state
+ * as d_prev and the number of earlier accesses to the key as d_ordinal; then every word c is replaced by the access's payload
+ * (rule[c] NX_CHAIN_GIVEN: d_payload[c] at its element, 0 where that pointer is NULL) or has delta[c] added to it modulo 2^32
+ * (NX_CHAIN_ADD; d_payload[c] must be NULL).  rule and delta belong to the stream: a column may be ADD in one stream and GIVEN in
+ * another.  The summary's d_last[c] is the state after the last access to the key, whatever the rules.  Words are raw 32-bit integers:
+ * nothing in device memory is validated for canonicity (as nx_trace_keccak_memory_check); only init must be below p.
+ * Rows and records that do not access (d_flag word == 0) get 0 in every output word of theirs; every output word is written.
+ * With no block stream and every rule GIVEN each output word equals nx_trace_prev_access's on the same streams.
+ * Exact and order-free: only integers are compared, counted, added and copied; every run gives the same words.  Blocks meet at kernel
+ * boundaries only.
+ * NX_ERR_ARG (nx_last_error names the argument; nothing is launched, nothing stays allocated): everything nx_trace_prev_access
+ * refuses (for column streams: log_size; 2^31 ELEMENTS or more in all, an element being a row of a column stream or one of the
+ * n_records * span accesses of a block stream); a span of 0 or above 256; more than 8 block streams; NX_CHAIN_BYTES on a column
+ * stream, on an ADD column, with span % 4 != 0 or with a payload pointer that is not 4-byte aligned; an ADD column with a non-NULL
+ * d_payload[c]; a rule word that is none of these.
+ * NX_ERR_PROTOCOL (outputs unspecified, the context stays usable; nx_last_error names the smallest offender by stream, then storage
+ * position or record, then sub-access): an accessing row or record with a key entry >= 2^key_bits[i] ("stream 2 record 3: key entry 0
+ * holds 300, outside its 8 bits"); a sub-access key at or above 2^(sum of key_bits) ("stream 1 record 4 sub-access 7: key 4294967290
+ * + 7 is outside the 32 key bits"); a d_row that is not strictly ascending, named at the first record whose row is not above its
+ * predecessor's ("stream 1 record 2: d_row of 5 is not above its predecessor's 9"), or not below 2^31.  These are read back before
+ * anything is sorted.
+ * DEVICE MEMORY: with A = the elements of all streams (accessing or not) and S = n_streams,
+ *     peak above the caller's columns  <=  18 A + 1024 S + 65536 bytes
+ * (two (key, handle) buffers of 8 A each; the per-block digit counts, A at most and never above 1 MiB; per 1024 sorted elements the
+ * head count, the last head and two words per chained column) and NOTHING per distinct key.  Taken from the context's allocator,
+ * released before the call returns.  Blocking.  Sort passes as nx_trace_prev_access.  Every column may lie at any word-aligned
+ * address. */
+#define NX_CHAIN_GIVEN 0u  /* the access leaves d_payload[c] behind (NULL pointer: 0): the rule of nx_trace_prev_access           */
+#define NX_CHAIN_ADD   1u  /* the access leaves (what it found + delta[c]) mod 2^32 behind; d_payload[c] must be NULL              */
+#define NX_CHAIN_BYTES 2u  /* ORed to GIVEN, block streams only: d_payload[c] holds `span` BYTES per record                        */
+typedef struct nx_chain_stream {
+    const uint32_t* const* d_key;      /* n_key_cols columns: the key of sub-access 0                                  */
+    const uint32_t* d_flag;            /* NULL: every row / record accesses                                            */
+    const uint32_t* d_row;             /* NULL: a COLUMN stream (as nx_access_stream).  Else a BLOCK stream: n_records  */
+                                       /* words, strictly ascending natural rows < 2^31; record j happens at d_row[j]  */
+    const uint32_t* const* d_payload;  /* n_payload entries                                                            */
+    const uint32_t* rule;              /* n_payload words (host), NULL = all NX_CHAIN_GIVEN                            */
+    const uint32_t* delta;             /* n_payload words (host, read for ADD columns), NULL = all 1                   */
+    uint32_t* const* d_prev;           /* NULL, or n_payload outputs (entries may be NULL)                             */
+    uint32_t* d_ordinal;               /* NULL, or output                                                              */
+    uint32_t log_size;                 /* column stream                                                                */
+    uint32_t n_records, span;          /* block stream: 0 <= n_records, 1 <= span <= 256                               */
+    uint32_t epoch, linear;
+} nx_chain_stream;
+int nx_trace_access_chain(nx_ctx* ctx, const nx_chain_stream* streams, uint32_t n_streams, uint32_t n_key_cols,
+                          const uint32_t* key_bits, uint32_t n_payload, const uint32_t* init, const nx_access_summary* summary,
+                          uint64_t* n_keys);
+
 /* ------------------------------------------- derived trace columns filled on the device from a recorded ROW PROGRAM --------------
  * The reference fills the main trace on the CPU: MachineChip::fill_main_trace (prover/src/traits.rs:34-40) runs every chip on every
  * row, and almost every chip is a row-local integer function of a few seed columns — AddChip's ValueA bytes and CarryFlag bits from

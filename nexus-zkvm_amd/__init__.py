@@ -631,6 +631,9 @@ class LookupUse(C.Structure):
     _fields_ = [("d_values", C.c_void_p), ("d_weight", C.c_void_p), ("log_size", C.c_uint32)]
 
 
+CHAIN_GIVEN, CHAIN_ADD, CHAIN_BYTES = 0, 1, 2     # NX_CHAIN_* of include/nexus_hip.h
+
+
 class AccessStream(C.Structure):
     """nx_access_stream of include/nexus_hip.h."""
     _fields_ = [("d_key", C.c_void_p), ("d_flag", C.c_void_p), ("d_payload", C.c_void_p), ("d_prev", C.c_void_p), ("d_ordinal", C.c_void_p),
@@ -640,6 +643,13 @@ class AccessStream(C.Structure):
 class AccessSummary(C.Structure):
     """nx_access_summary of include/nexus_hip.h."""
     _fields_ = [("cap", C.c_uint32), ("d_key", C.c_void_p), ("d_count", C.c_void_p), ("d_last", C.c_void_p)]
+
+
+class ChainStream(C.Structure):
+    """nx_chain_stream of include/nexus_hip.h."""
+    _fields_ = [("d_key", C.c_void_p), ("d_flag", C.c_void_p), ("d_row", C.c_void_p), ("d_payload", C.c_void_p), ("rule", C.c_void_p), ("delta", C.c_void_p),
+                ("d_prev", C.c_void_p), ("d_ordinal", C.c_void_p), ("log_size", C.c_uint32), ("n_records", C.c_uint32), ("span", C.c_uint32), ("epoch", C.c_uint32),
+                ("linear", C.c_uint32)]
 
 
 class PartLimb(C.Structure):
@@ -1479,6 +1489,58 @@ class HipBackend:
         n = C.c_uint64(0)
         rc = self.L.nx_trace_prev_access(self.ctx, arr, len(streams), k, kb.ctypes.data_as(C.c_void_p), n_payload, iv.ctypes.data_as(C.c_void_p) if iv is not None else None,
                                          C.byref(sm) if sm is not None else None, C.byref(n))
+        if want_rc and rc in (NX_OK, NX_ERR_PROTOCOL):
+            return (n.value if rc == NX_OK else None), rc
+        self._chk(rc)
+        return n.value
+
+    def trace_access_chain(self, streams, key_bits, n_payload, init=None, summary=None, want_rc=False):
+        """nx_trace_access_chain: trace_prev_access for accesses that leave behind what depends on what they found, and for block
+        records.  streams: the dicts of trace_prev_access, and further — rule: n_payload words of CHAIN_GIVEN / CHAIN_ADD
+        (| CHAIN_BYTES), absent: all GIVEN; delta: n_payload words added by the ADD columns, absent: all 1; row: device pointer of
+        n_records strictly ascending natural rows, which makes the stream a BLOCK stream of n_records records of `span` accesses to
+        key + i (key and flag then hold one word per record, payload / prev / ordinal one word per access, record-major; a
+        CHAIN_BYTES payload one byte per access).  Returns the number of distinct keys; raises as the neighbours do, also on
+        NX_ERR_PROTOCOL (a key outside its bits, rows that do not ascend) unless want_rc: then (n_keys or None, code)."""
+        kb = _u32(key_bits).reshape(-1)
+        k, n_payload = len(kb), int(n_payload)
+
+        def table(ptrs, n, what, i):
+            if ptrs is None:
+                return None
+            if len(ptrs) != n:
+                raise NexusHipError(f"trace_access_chain: stream {i} has {len(ptrs)} {what} columns, {n} expected")
+            t = (C.c_void_p * max(1, n))(*[int(x) if x else None for x in ptrs])
+            keep.append(t)
+            return C.cast(t, C.c_void_p)
+
+        def words(vals, what, i):
+            if vals is None:
+                return None
+            if len(vals) != n_payload:
+                raise NexusHipError(f"trace_access_chain: stream {i} has {len(vals)} {what} words, {n_payload} expected")
+            t = (C.c_uint32 * max(1, n_payload))(*[int(x) & 0xFFFFFFFF for x in vals])
+            keep.append(t)
+            return C.cast(t, C.c_void_p)
+
+        arr, keep = (ChainStream * max(1, len(streams)))(), []
+        for i, s in enumerate(streams):
+            arr[i] = ChainStream(table(s["key"], k, "key", i), int(s["flag"]) if s.get("flag") else None, int(s["row"]) if s.get("row") else None,
+                                 table(s.get("payload"), n_payload, "payload", i), words(s.get("rule"), "rule", i), words(s.get("delta"), "delta", i),
+                                 table(s.get("prev"), n_payload, "prev", i), int(s["ordinal"]) if s.get("ordinal") else None, int(s.get("log_size", 0)),
+                                 int(s.get("n_records", 0)), int(s.get("span", 0)), int(s.get("epoch", 0)), int(bool(s.get("linear", False))))
+        iv = None
+        if init is not None:
+            iv = _u32(init).reshape(-1)
+            if len(iv) != n_payload:
+                raise NexusHipError(f"trace_access_chain: {len(iv)} init words for {n_payload} payload columns")
+        sm = None
+        if summary is not None:
+            cap, key_ptr, count_ptr, last_ptrs = summary
+            sm = AccessSummary(int(cap), int(key_ptr) if key_ptr else None, int(count_ptr) if count_ptr else None, table(last_ptrs, n_payload, "summary last", "-"))
+        n = C.c_uint64(0)
+        rc = self.L.nx_trace_access_chain(self.ctx, arr, len(streams), k, kb.ctypes.data_as(C.c_void_p), n_payload, iv.ctypes.data_as(C.c_void_p) if iv is not None else None,
+                                          C.byref(sm) if sm is not None else None, C.byref(n))
         if want_rc and rc in (NX_OK, NX_ERR_PROTOCOL):
             return (n.value if rc == NX_OK else None), rc
         self._chk(rc)

@@ -475,6 +475,26 @@ impl Session {
                                                       if init.is_empty() { std::ptr::null() } else { init.as_ptr() }, summary.map_or(std::ptr::null(), |s| s as *const _), &mut n))?;
         Ok(n)
     }
+    /// `trace_prev_access` for accesses that leave behind what depends on what they found (`nx_trace_access_chain`): the RAM of a
+    /// machine that runs the keccak precompile.  `KeccakChip::update_state_timestamps` (prover/src/chips/custom.rs:107-123) reports
+    /// the timestamp it finds at each of 200 bytes and leaves `ts + 1`, so calls on one buffer chain through each other.  A stream
+    /// with a null `d_row` is an `nx_access_stream`; with `d_row` it is a list of `n_records` records of `span` accesses to key + i
+    /// at natural row `d_row[j]` (the keccak instances).  `rule[c]` is `NX_CHAIN_GIVEN`, `NX_CHAIN_ADD` (the access leaves what it
+    /// found + `delta[c]`) or `NX_CHAIN_GIVEN | NX_CHAIN_BYTES` (a block stream's payload holds bytes, the layout of
+    /// `d_states_out`); `d_prev` of the timestamp column of the block stream is what `trace_keccak_memory_check` takes as
+    /// `d_timestamps`.  Returns the number of distinct keys.  A key outside its bits or a `d_row` that does not ascend is `HipError`
+    /// from NX_ERR_PROTOCOL, naming stream, record and sub-access.
+    ///
+    /// # Safety
+    /// Every pointer inside `streams` and `summary` must be valid for the sizes the header states; outputs must not alias.
+    pub unsafe fn trace_access_chain(&mut self, streams: &[sys::nx_chain_stream], key_bits: &[u32], n_payload: u32, init: &[u32], summary: Option<&sys::nx_access_summary>)
+        -> Result<u64, HipError> {
+        if !init.is_empty() && init.len() != n_payload as usize { return Err(HipError::Argument("trace_access_chain: one init word per payload column".into())); }
+        let mut n = 0u64;
+        try_check(self.ctx, sys::nx_trace_access_chain(self.ctx, streams.as_ptr(), streams.len() as u32, key_bits.len() as u32, key_bits.as_ptr(), n_payload,
+                                                       if init.is_empty() { std::ptr::null() } else { init.as_ptr() }, summary.map_or(std::ptr::null(), |s| s as *const _), &mut n))?;
+        Ok(n)
+    }
     /// The KeccakRound component's trace filled on the device (`nx_trace_keccak_round`): what the reference's
     /// `generate_round_component_trace` builds on the CPU from `convert_input_to_simd`'s rows (prover/src/extensions/keccak/round/
     /// trace.rs:240-366).  `d_states`: `n_instances` x 25 lanes in device memory (null when there are none); natural row
@@ -628,6 +648,10 @@ impl Drop for Verifier { fn drop(&mut self) { unsafe { sys::nx_verifier_destroy(
 pub struct TracePartition { #[allow(dead_code)] ctx: *mut sys::nx_ctx, h: *mut sys::nx_partition }
 impl Drop for TracePartition { fn drop(&mut self) { unsafe { sys::nx_trace_partition_destroy(self.h) } } }
 /// `NX_PART_NONE`: the class word of a step that belongs to no component; `NX_PART_ALL`: the class of a destination that takes every step.
+/// Rule words of `nx_chain_stream` (`NX_CHAIN_*` of the header).
+pub const CHAIN_GIVEN: u32 = 0;
+pub const CHAIN_ADD: u32 = 1;
+pub const CHAIN_BYTES: u32 = 2;
 pub const PART_NONE: u32 = 0xFFFF_FFFF;
 pub const PART_ALL: u32 = 0xFFFF_FFFF;
 /// `num.next_power_of_two().ilog2().max(LOG_N_LANES)` of the v2 components' `generate_main_trace` (`nx_trace_partition_log_size`).
