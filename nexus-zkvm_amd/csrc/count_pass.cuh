@@ -1,4 +1,4 @@
-// One stable 8-bit counting pass over `total` elements, shared by the trace fillers that sort or partition on the device (prev_access.hip:
+// One stable 8-bit counting pass over `total` elements, shared by the trace fillers that sort or partition on the device (access_history.cuh:
 // every pass of its LSD radix sort; trace_partition.hip: its one pass over the class column).  ONE text, included inside namespace nx
 // after internal.h and <algorithm>.  Three launches, blocks communicate at the kernel boundaries only:
 //   histogram   a block takes tiles * 256 consecutive elements and counts its digits: hist[digit * blocks + block].

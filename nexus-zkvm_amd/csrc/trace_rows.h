@@ -1,6 +1,6 @@
 // Natural coset row <-> storage position of a trace column (bit-reversed circle-domain order; reference
 // prover/src/trace/utils_external.rs:24-39).  ONE text with two readers: the translation units that compile it (logup.hip,
-// prev_access.hip) and air_jit.hip, which defines NX_TRACE_ROWS_AS_TEXT and takes it as a string literal into the preludes of the
+// access_history.cuh) and air_jit.hip, which defines NX_TRACE_ROWS_AS_TEXT and takes it as a string literal into the preludes of the
 // kernels hiprtc compiles (TRACE_ROWS_PRELUDE; FI is those preludes' own macro).  No preprocessor lines and no string literals inside
 // the parentheses.  bitrev: field.cuh / AIR_PRELUDE.
 #ifdef NX_TRACE_ROWS_AS_TEXT

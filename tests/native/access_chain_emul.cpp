@@ -1,9 +1,9 @@
-// nx_trace_access_chain on the host: csrc/access_chain.hip compiled as plain C++ against tests/native/prev_emul/internal.h (256 lock-step
+// nx_trace_access_chain on the host: csrc/access_chain.hip (with csrc/access_history.cuh) compiled as plain C++ against tests/native/prev_emul/internal.h (256 lock-step
 // threads per block as fibers, waves of 64 with ballot / shuffle, LDS as static storage), so the entry point with its kernels is checked
 // word for word against a sequential walk over a map — under the address and undefined-behaviour sanitizers, which watch every LDS,
 // histogram, placement, aggregate and summary index; every output has guard words behind it.  Built twice by the test: as it is, and with
 // -DNX_COUNT_PASS_MAX_BLOCKS=2, where a block of the sort takes more tiles than the minimum.
-#include "access_chain_emu.cpp"   // a copy of csrc/access_chain.hip next to the shim internal.h, trace_rows.h and count_pass.cuh (the test makes it)
+#include "access_chain_emu.cpp"   // a copy of csrc/access_chain.hip next to the shim internal.h, access_history.cuh, trace_rows.h and count_pass.cuh (the test makes it)
 #include <random>
 #include <map>
 #include <tuple>

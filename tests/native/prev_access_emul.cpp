@@ -1,9 +1,9 @@
-// nx_trace_prev_access on the host: csrc/prev_access.hip compiled as plain C++ against tests/native/prev_emul/internal.h (256 lock-step
+// nx_trace_prev_access on the host: csrc/prev_access.hip (with csrc/access_history.cuh) compiled as plain C++ against tests/native/prev_emul/internal.h (256 lock-step
 // threads per block as fibers, waves of 64 with ballot / shuffle, LDS as static storage), so the entry point with its kernels is checked
 // against a sequential walk over a map — under the address and undefined-behaviour sanitizers, which watch every LDS, histogram and
 // placement index.  Built twice by the test: as it is, and with -DNX_COUNT_PASS_MAX_BLOCKS=2, where a block of the sort takes more tiles
 // than the minimum.
-#include "prev_access_emu.cpp"   // a copy of csrc/prev_access.hip next to the shim internal.h, trace_rows.h and count_pass.cuh (the test makes it)
+#include "prev_access_emu.cpp"   // a copy of csrc/prev_access.hip next to the shim internal.h, access_history.cuh, trace_rows.h and count_pass.cuh (the test makes it)
 #include <random>
 #include <map>
 
@@ -185,6 +185,23 @@ int main() {
             st[0].key[0][511] = P - 1;
             run_case("  and in the stream without flags", st, bits, 5, init, false, ~0u, NX_ERR_PROTOCOL);
         }
+    }
+    for (const std::vector<u32>& bits : std::vector<std::vector<u32>>{{8}, {8, 8, 8, 8}}) {
+        // No flag anywhere and whole-byte keys: the last pass has no digit to spare, so a refused row (key 0, no handle) takes digit 255
+        // like the real keys with top byte 255 and stands among them by its lower bytes, then by time.  Key 255 << (bits - 8) has the
+        // same lower bytes (none, or zeros), so in time order K, refused, K, refused, K is also their sorted order: the resolve meets
+        // elements without a handle with real ones on both sides.
+        const std::vector<u32> init{P - 1, 7, 0, P - 2, 1};
+        std::vector<Stream> st; for (u32 s = 0; s < 3; s++) st.push_back(make_stream(bits, 9, 5, 0, false, 0));
+        const auto pos_of_row = [](u32 row) { u32 pos = 0; while (model_row_of_pos(pos, 9) != row) pos++; return pos; };
+        const auto put = [&](u32 s, u32 row, bool refused) {
+            const u32 pos = pos_of_row(row);
+            for (size_t c = 0; c < bits.size(); c++) st[s].key[c][pos] = !refused && c + 1 == bits.size() ? 255u : 0u;
+            if (refused) st[s].key[0][pos] = 256;       // a word of 9 bits in a column of 8
+        };
+        put(0, 10, false); put(1, 20, true); put(2, 30, false); put(0, 40, true); put(1, 50, false);
+        run_case(bits.size() == 1 ? "  refused rows between keys of digit 255, one pass" : "  refused rows between keys of digit 255, four passes", st, bits, 5, init, true, ~0u,
+                 NX_ERR_PROTOCOL);
     }
     {   // 2^11 + 2 elements: with a block cap of 2 (the test's second build) a sort block takes five tiles, one more than the minimum, in
         // every one of the two passes (13 key bits and flags); as built it is two blocks of four tiles and one of one

@@ -955,7 +955,7 @@ def _air_eval(log, sh, rng, variant):
 
 # ------------------------------------------------------------------------------------------------------------------ trace fills
 
-@entry("nx_trace_prev_access", "fills", "B", ("prev_access.hip:292 vec = n >= 4 && aligned", "prev_access.hip:62 gld4_guarded", "prev_access.hip:68", "prev_access.hip:88 gst4 of all-idle quads", "prev_access.hip:89"),
+@entry("nx_trace_prev_access", "fills", "B", ("access_history.cuh:532 vec = n >= 4 && aligned", "access_history.cuh:164 gld4_guarded", "access_history.cuh:170", "access_history.cuh:188 gst4 of all-idle quads", "access_history.cuh:189"),
        sizes=(1, 2, 3, 5, 6), vector_from="2^2 rows of a stream (one quad)")
 def _prev_access(log, sh, rng, variant):
     import prev_access_model as M

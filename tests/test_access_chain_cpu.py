@@ -186,7 +186,7 @@ def test_every_refusal_is_reached_with_a_null_context_and_names_its_argument():
 
 
 def test_kernels_in_lock_step_on_the_host_under_sanitizers(tmp_path):
-    """csrc/access_chain.hip as host C++ (tests/native/prev_emul/internal.h: 256 lock-step fibers per block, waves of 64): GIVEN-only
+    """csrc/access_chain.hip with csrc/access_history.cuh as host C++ (tests/native/prev_emul/internal.h: 256 lock-step fibers per block, waves of 64): GIVEN-only
     calls, one key chained 1 .. 3000 times with a GIVEN at the start, the middle and the end, column and block streams mixed at every
     span and record count with random rules, bytes, flags, NULL columns, epochs, misplaced buffers and short summaries, an absorb loop,
     keys up to 2^32 - 1 and every refusal of the device against a walk over a map, with ASan and UBSan watching every LDS, histogram,
@@ -198,6 +198,7 @@ def test_kernels_in_lock_step_on_the_host_under_sanitizers(tmp_path):
     shutil.copy(os.path.join(csrc, "access_chain.hip"), str(tmp_path / "access_chain_emu.cpp"))
     shutil.copy(os.path.join(csrc, "trace_rows.h"), str(tmp_path / "trace_rows.h"))
     shutil.copy(os.path.join(csrc, "count_pass.cuh"), str(tmp_path / "count_pass.cuh"))
+    shutil.copy(os.path.join(csrc, "access_history.cuh"), str(tmp_path / "access_history.cuh"))
     shutil.copy(os.path.join(native, "prev_emul", "internal.h"), str(tmp_path / "internal.h"))
     for cap, flags in ((1024, []), (2, ["-DNX_COUNT_PASS_MAX_BLOCKS=2"])):
         exe = str(tmp_path / ("access_chain_emul_%d" % cap))

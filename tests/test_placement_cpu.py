@@ -108,7 +108,7 @@ def test_the_dispatch_thresholds_are_the_sources():
     assert f"FUSED_MIN_LOG = {PL.FUSED_LOG}" in source_line("merkle.hip:601")
     assert "MULT_TILE = MULT_THREADS * MULT_QUADS * 4" in source_line("multiplicity.hip:27") and 256 * 4 * 4 == 1 << PL.MULT_TILE_LOG
     assert "SC_MIN_LOG = SC_H + SC_T + 1" in source_line("logup.hip:293") and "SC_H = 7, SC_T = 5" in source_line("logup.hip:293") and PL.SCAN_TILED_LOG == 13
-    assert "n >= 4 && !(align & 15)" in source_line("prev_access.hip:292")
+    assert "n >= 4 && !(align & 15)" in source_line("access_history.cuh:532")
     assert "n >= per_lane && !((uintptr_t)d_cols[c] & 15)" in source_line("fft.hip:783")
     assert "(n_words & 3) || ((uintptr_t)d_dst & 15) || ((uintptr_t)d_src & 15)" in source_line("ctx.hip:511")
     assert "& 15)) vec4 = false" in source_line("air_jit.hip:1603")

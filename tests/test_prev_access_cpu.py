@@ -146,22 +146,30 @@ def test_every_refusal_is_reached_with_a_null_context_and_names_its_argument():
 
 def test_coset_row_mapping_has_one_text():
     """pos_of_coset_row / coset_row_of_pos live in csrc/trace_rows.h alone: the kernels compiled ahead of time include it as code, the
-    preludes of the generated kernels take it as text."""
+    preludes of the generated kernels take it as text.  In the same way what nx_trace_prev_access and nx_trace_access_chain share lives in
+    csrc/access_history.cuh alone: the time-index formula, the sort policy and the quad load of the resolve are defined there and in no
+    other file, and the two entries' files include it."""
     csrc = os.path.join(ROOT, "nexus-zkvm_amd", "csrc")
+    one_text = {"pos_of_coset_row": r"u32 pos_of_coset_row\(u32 \w+, int log\) \{", "coset_row_of_pos": r"u32 coset_row_of_pos\(u32 \w+, int log\) \{",
+                "time index": r"u32 \w*time_index\([^)]*\) \{", "the formula itself": r"\+ r \* \w+(?:->|\.)ge\[b\] \+", "sort policy": r"struct \w+Sort \{\s*const u32\* kin; const u32\* vin; u32\* kout; u32\* vout; \w+Pass ps;",
+                "load_quad": r"void \w*load_quad\([^)]*\) \{"}
     defs = {}
     for name in sorted(os.listdir(csrc)) + ["host/" + n for n in sorted(os.listdir(os.path.join(csrc, "host")))]:
         if os.path.isfile(os.path.join(csrc, name)) and name.endswith((".hip", ".h", ".cuh", ".cpp")):
             text = open(os.path.join(csrc, name)).read()
-            for fn in ("pos_of_coset_row", "coset_row_of_pos"):
-                if re.search(r"u32 %s\(u32 \w+, int log\) \{" % fn, text):
-                    defs.setdefault(fn, []).append(name)
-    assert defs == {"pos_of_coset_row": ["trace_rows.h"], "coset_row_of_pos": ["trace_rows.h"]}, defs
-    for user in ("air_jit.hip", "logup.hip", "prev_access.hip"):
+            for what, pattern in one_text.items():
+                defs.setdefault(what, []).extend([name] * len(re.findall(pattern, text)))
+    assert defs == {"pos_of_coset_row": ["trace_rows.h"], "coset_row_of_pos": ["trace_rows.h"], "time index": ["access_history.cuh"],
+                    "the formula itself": ["access_history.cuh"], "sort policy": ["access_history.cuh"], "load_quad": ["access_history.cuh"]}, defs
+    for user in ("air_jit.hip", "logup.hip", "access_history.cuh"):
         assert '#include "trace_rows.h"' in open(os.path.join(csrc, user)).read()
+    for user in ("prev_access.hip", "access_chain.hip"):
+        text = open(os.path.join(csrc, user)).read()
+        assert '#include "access_history.cuh"' in text and "__global__" not in text and "struct " not in text, user
 
 
 def test_both_readers_of_the_coset_row_text_compute_the_models_mapping(tmp_path):
-    """csrc/trace_rows.h as code (what logup.hip and prev_access.hip compile) and as the text inside a generated kernel's source (what
+    """csrc/trace_rows.h as code (what logup.hip and access_history.cuh compile) and as the text inside a generated kernel's source (what
     hiprtc compiles), both built as host C++: the same rows as the model's definition at every position of 2^1 .. 2^10 rows, and
     pos_of_coset_row is the inverse."""
     nz, _ = _lib()
@@ -187,9 +195,9 @@ def test_both_readers_of_the_coset_row_text_compute_the_models_mapping(tmp_path)
 
 
 def test_kernels_in_lock_step_on_the_host_under_sanitizers(tmp_path):
-    """csrc/prev_access.hip as host C++ (tests/native/prev_emul/internal.h: 256 lock-step fibers per block, waves of 64): every key
+    """csrc/prev_access.hip with csrc/access_history.cuh as host C++ (tests/native/prev_emul/internal.h: 256 lock-step fibers per block, waves of 64): every key
     shape, stream count, size up to 2^12 rows, flag / ordinal / summary / NULL-column choice, the skewed inputs, epochs and mixed
-    sizes, short summaries, rows out of range and a refusal against a walk over a map, with ASan and UBSan watching every LDS,
+    sizes, short summaries, rows out of range (also refused rows sorted between real keys) and a refusal against a walk over a map, with ASan and UBSan watching every LDS,
     histogram, placement and summary index — and the device-memory bound of the header.  Twice: as built, and with a block cap of 2,
     where a block of the sort takes up to eight tiles and the case of 2^11 + 2 elements takes five in each of its two passes."""
     gxx = shutil.which("g++")
@@ -198,6 +206,7 @@ def test_kernels_in_lock_step_on_the_host_under_sanitizers(tmp_path):
     shutil.copy(os.path.join(csrc, "prev_access.hip"), str(tmp_path / "prev_access_emu.cpp"))
     shutil.copy(os.path.join(csrc, "trace_rows.h"), str(tmp_path / "trace_rows.h"))
     shutil.copy(os.path.join(csrc, "count_pass.cuh"), str(tmp_path / "count_pass.cuh"))
+    shutil.copy(os.path.join(csrc, "access_history.cuh"), str(tmp_path / "access_history.cuh"))
     shutil.copy(os.path.join(native, "prev_emul", "internal.h"), str(tmp_path / "internal.h"))
     for cap, flags in ((1024, []), (2, ["-DNX_COUNT_PASS_MAX_BLOCKS=2"])):
         exe = str(tmp_path / ("prev_access_emul_%d" % cap))
@@ -207,6 +216,7 @@ def test_kernels_in_lock_step_on_the_host_under_sanitizers(tmp_path):
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
         assert "\n0 failures" in r.stdout and r.stdout.count(" OK ") >= 71 and "FAIL" not in r.stdout and ("block cap %d\n" % cap) in r.stdout
         assert "linear streams of 2^11 and 2 rows " in r.stdout and "PLAN NOT REACHED" not in r.stdout
+        assert "refused rows between keys of digit 255, one pass " in r.stdout and "refused rows between keys of digit 255, four passes " in r.stdout
         assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
 
 
