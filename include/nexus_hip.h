@@ -107,6 +107,12 @@ int nx_ctx_set_hash_mode(nx_ctx* ctx, int mode);
  * proofs of that shape — nx_prover_tree_adopt's rule; statements with a table component still fill theirs), "trace.vec4" (1, the default: nx_trace_program runs a program whose loads all have offset 0 with four
  * storage positions per lane — 16-byte loads and stores — instead of one row per lane).  "host.pack_threads" (1..64; default
  * min(16, hardware threads)): host threads that pack NX_COL_U32_AS_U16 / NX_COL_U32_AS_U8 columns of the narrow upload entry points.
+ * Debug aids of the device block cache (default 0, NX_DEBUG_POISON / NX_DEBUG_POISON_FREE): "debug.poison" (1, 2, 3: every block the
+ * context's allocator hands out — nx_alloc and every internal temporary, fresh or recycled — is filled whole with 0xA5A5A5A5, 0xFFFFFFFF
+ * or 0x00000001 first, on the stream its owner's first write would take, with no synchronisation; the staging ring of pointer tables and
+ * constants is filled when the option turns on and again where it wraps) and "debug.poison_free" (1, with "debug.poison" != 0: a block is
+ * filled again when it goes back to the cache).  Code that reads a temporary before it wrote all of it, or frees a block something
+ * still reads, then computes from the pattern instead of from zero pages or a previous call's values.
  * Unknown names and out-of-range values are NX_ERR_ARG.
  * None of them changes a result: proofs, roots and transforms are bit-identical under every setting. */
 int nx_ctx_set_option(nx_ctx* ctx, const char* name, int64_t value);

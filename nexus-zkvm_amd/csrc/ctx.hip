@@ -23,13 +23,31 @@ int hip_fail(nx_ctx* ctx, hipError_t e, const char* what, const char* file, int 
     return set_err(ctx, e == hipErrorOutOfMemory ? NX_ERR_OOM : NX_ERR_HIP, buf);
 }
 
+// "debug.poison": the first `bytes` of both halves of the staging ring hold the pattern, so a reader that runs past the staged bytes of
+// its slot sees it.  The caller has drained every stream that reads the ring.
+static int poison_ring(nx_ctx* ctx, size_t bytes) {
+    const uint32_t w = poison_word(ctx->opt.debug_poison);
+    if (!bytes) return NX_OK;
+    for (size_t i = 0; i < bytes / 4; i++) ((uint32_t*)ctx->h_scratch)[i] = w;
+    NX_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->d_scratch, (int)w, bytes / 4, ctx->stream));
+    return NX_OK;
+}
+// What a wrap leaves as it is: the last slots of the lap may belong to a call that staged its tables and has yet to launch their reader
+// (a slot stays intact until the next lap reaches it: what every call with more than one slot relies on).
+constexpr size_t RING_POISON_SPARE = (size_t)1 << 20;
+static int drain_ring_readers(nx_ctx* ctx) {
+    NX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 3; i++) NX_HIP(ctx, hipStreamSynchronize(ctx->side[i]));
+    return NX_OK;
+}
+
 int stage(nx_ctx* ctx, const void* h_src, size_t bytes, void** d_out) {
     size_t need = (bytes + 255) & ~(size_t)255;
     if (need > ctx->scratch_size) return set_err(ctx, NX_ERR_ARG, "stage: request larger than scratch ring");
     if (ctx->scratch_off + need > ctx->scratch_size) {
         // wrap: make sure every earlier consumer of the ring has finished
-        NX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < 3; i++) NX_HIP(ctx, hipStreamSynchronize(ctx->side[i]));
+        NX_TRY(drain_ring_readers(ctx));
+        if (ctx->opt.debug_poison && ctx->scratch_off > RING_POISON_SPARE) NX_TRY(poison_ring(ctx, ctx->scratch_off - RING_POISON_SPARE));
         ctx->scratch_off = 0;
     }
     memcpy(ctx->h_scratch + ctx->scratch_off, h_src, bytes);
@@ -149,6 +167,20 @@ int check_aligned(nx_ctx* ctx, const char* entry, const char* arg, const void* c
                                         std::to_string(align) + "-byte words)");
 }
 
+// "debug.poison": the fill stands for the next owner's first write (dev_alloc) or for the block's next life (dev_free), so it is
+// enqueued where that write would be, on ctx->cur, and synchronises nothing: an ordering a site never established stays missing.
+static hipError_t poison_block(nx_ctx* ctx, void* p, size_t bytes) {
+    return hipMemsetD32Async((hipDeviceptr_t)p, (int)poison_word(ctx->opt.debug_poison), bytes / 4, ctx->cur);
+}
+static int dev_alloc_poisoned(nx_ctx* ctx, size_t bytes, void** out) {
+    const hipError_t e = poison_block(ctx, *out, bytes);
+    if (e == hipSuccess) return NX_OK;
+    ctx->live_blocks.erase(*out); ctx->live_bytes -= bytes;       // back to the cache: the caller gets no block
+    ctx->free_blocks.insert({bytes, *out}); ctx->cached_bytes += bytes;
+    *out = nullptr;
+    return hip_fail(ctx, e, "hipMemsetD32Async (debug.poison)", __FILE__, __LINE__);
+}
+
 int dev_alloc(nx_ctx* ctx, size_t bytes, void** out) {
     if (bytes == 0) bytes = 4;
     bytes = (bytes + 255) & ~(size_t)255;
@@ -157,7 +189,7 @@ int dev_alloc(nx_ctx* ctx, size_t bytes, void** out) {
         *out = it->second; ctx->free_blocks.erase(it); ctx->cached_bytes -= bytes;
         ctx->live_blocks[*out] = bytes;
         ctx->live_bytes += bytes; ctx->peak_live_bytes = std::max(ctx->peak_live_bytes, ctx->live_bytes);
-        return NX_OK;
+        return ctx->opt.debug_poison ? dev_alloc_poisoned(ctx, bytes, out) : NX_OK;
     }
     hipError_t e = hipMalloc(out, bytes);
     if (e == hipErrorOutOfMemory) {  // give cached blocks back to the driver and retry once
@@ -168,12 +200,13 @@ int dev_alloc(nx_ctx* ctx, size_t bytes, void** out) {
     if (e != hipSuccess) { *out = nullptr; return hip_fail(ctx, e, "hipMalloc", __FILE__, __LINE__); }
     ctx->live_blocks[*out] = bytes;
     ctx->live_bytes += bytes; ctx->peak_live_bytes = std::max(ctx->peak_live_bytes, ctx->live_bytes);
-    return NX_OK;
+    return ctx->opt.debug_poison ? dev_alloc_poisoned(ctx, bytes, out) : NX_OK;
 }
 void dev_free(nx_ctx* ctx, void* p) {
     if (!p) return;
     auto it = ctx->live_blocks.find(p);
     if (it == ctx->live_blocks.end()) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(p); return; }  // foreign pointer
+    if (ctx->opt.debug_poison && ctx->opt.debug_poison_free) (void)poison_block(ctx, p, it->second);
     ctx->free_blocks.insert({it->second, p});
     ctx->cached_bytes += it->second;
     ctx->live_bytes -= it->second;
@@ -340,6 +373,8 @@ static nx_options options_from_env() {
     o.machine_reuse_pre = env_int("NX_MACHINE_REUSE_PREPROCESSED", 0) != 0;
     o.machine_logup_program = env_int("NX_MACHINE_LOGUP_PROGRAM", 0) != 0;
     o.trace_vec4 = env_int("NX_TRACE_VEC4", 1) != 0;   // profiles/trace_program_bench.json: 0.180 ms against 0.196 ms for 41 columns of 2^22 rows
+    o.debug_poison = clampi(env_int("NX_DEBUG_POISON", 0), 0, 3);
+    o.debug_poison_free = env_int("NX_DEBUG_POISON_FREE", 0) != 0;
     o.host_pack_threads = clampi((int)std::thread::hardware_concurrency(), 1, 16);   // a GPU box grants a command 16 CPUs
     return o;
 }
@@ -369,13 +404,21 @@ static const OptEntry k_options[] = {
     {"machine.logup_program", &nx_options::machine_logup_program, 0, 1},
     {"trace.vec4", &nx_options::trace_vec4, 0, 1},
     {"host.pack_threads", &nx_options::host_pack_threads, 1, 64},
+    {"debug.poison", &nx_options::debug_poison, 0, 3},
+    {"debug.poison_free", &nx_options::debug_poison_free, 0, 1},
 };
 int nx_ctx_set_option(nx_ctx* ctx, const char* name, int64_t value) {
     if (!ctx || !name) return set_err(ctx, NX_ERR_ARG, "nx_ctx_set_option: NULL argument");
     for (const OptEntry& e : k_options)
         if (!strcmp(e.name, name)) {
             if (value < e.lo || value > e.hi) return set_err(ctx, NX_ERR_ARG, std::string("nx_ctx_set_option: value out of range for ") + name);
+            const int was_poison = ctx->opt.debug_poison;
             ctx->opt.*(e.field) = (int)value;
+            if (ctx->opt.debug_poison && ctx->opt.debug_poison != was_poison) {     // between two calls no slot of the staging ring is in use
+                NX_GUARD(ctx);
+                NX_TRY(drain_ring_readers(ctx));
+                NX_TRY(poison_ring(ctx, ctx->scratch_size));
+            }
             return NX_OK;
         }
     return set_err(ctx, NX_ERR_ARG, std::string("nx_ctx_set_option: unknown option ") + name);
@@ -426,6 +469,7 @@ int nx_ctx_create(int device, nx_ctx** out) {
     }
     NX_HIP(nullptr, hipMalloc((void**)&c->d_scratch, c->scratch_size));
     NX_HIP(nullptr, hipHostMalloc((void**)&c->h_scratch, c->scratch_size, hipHostMallocDefault));
+    if (c->opt.debug_poison) { const int rc = poison_ring(c, c->scratch_size); if (rc != NX_OK) { nx_ctx_destroy(c); return rc; } }
     *out = c;
     return NX_OK;
 }

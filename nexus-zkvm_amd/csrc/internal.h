@@ -38,6 +38,9 @@ struct nx_options {
     int air_degree_split;         // "air.degree_split": constraints of degree <= 3 of a component with a bound > 1 are evaluated on the log_size + 1 domain
     int trace_vec4;               // "trace.vec4": nx_trace_program runs a program whose loads are all row-local with four storage positions per lane (16-byte loads and stores) instead of one row per lane
     int host_pack_threads;        // "host.pack_threads": host threads that pack NX_COL_U32_AS_* columns (HostFeed)
+    // debug aids of the caching allocator ("poisoned blocks"); with both 0 dev_alloc / dev_free take one extra branch
+    int debug_poison;             // "debug.poison": 0 = off; 1, 2, 3: dev_alloc fills the whole rounded block, fresh or recycled, with 0xA5A5A5A5 / 0xFFFFFFFF / 0x00000001 on ctx->cur before it returns it; the staging ring is filled when the option turns on and at every wrap
+    int debug_poison_free;        // "debug.poison_free": while debug.poison != 0, dev_free fills a block it owns with the same pattern before it caches it
 };
 
 struct nx_ctx {
@@ -234,6 +237,8 @@ int eval_at_points_collect(nx_ctx* ctx, std::vector<EvalJob>* jobs);
 int dev_alloc(nx_ctx* ctx, size_t bytes, void** out);
 void dev_free(nx_ctx* ctx, void* p);
 void dev_cache_release(nx_ctx* ctx);
+// "debug.poison": the word dev_alloc / dev_free / the staging ring are filled with (pattern 1..3)
+inline uint32_t poison_word(int pattern) { return pattern == 1 ? 0xA5A5A5A5u : pattern == 2 ? 0xFFFFFFFFu : 0x00000001u; }
 
 // n_cols columns of n_words words each, dst[k] <- src[k], one launch (ctx.hip)
 int copy_columns(nx_ctx* ctx, uint32_t* const* h_dst, const uint32_t* const* h_src, uint32_t n_cols, size_t n_words);

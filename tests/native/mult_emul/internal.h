@@ -81,8 +81,16 @@ inline int make_colset(nx_ctx*, const uint32_t* const* h, uint32_t n, ColSet* ou
     for (uint32_t i = 0; i < n; i++) t[i] = (uint32_t*)h[i];
     out->table = t; return NX_OK;
 }
-inline int dev_alloc(nx_ctx* c, size_t bytes, void** out) { *out = aligned_alloc(256, (bytes + 255) & ~(size_t)255); c->live++; return NX_OK; }
-inline void dev_free(nx_ctx* c, void* p) { free(p); c->live--; }
+// A block never comes zeroed or with a previous owner's plausible words: dev_alloc fills the whole rounded block with 0xA5A5A5A5 (>= p,
+// nonzero), dev_free with 0xFFFFFFFF before the memory goes back.  The rounded size sits in a 256-byte header in front of the block.
+inline void fill_words(void* p, size_t bytes, u32 w) { for (size_t i = 0; i < bytes / 4; i++) ((u32*)p)[i] = w; }
+inline int dev_alloc(nx_ctx* c, size_t bytes, void** out) {
+    const size_t rounded = (std::max<size_t>(bytes, 4) + 255) & ~(size_t)255;
+    char* q = (char*)aligned_alloc(256, 256 + rounded); *(size_t*)q = rounded; *out = q + 256;
+    fill_words(*out, rounded, 0xA5A5A5A5u);
+    c->live++; return NX_OK;
+}
+inline void dev_free(nx_ctx* c, void* p) { if (!p) { c->live--; return; } char* q = (char*)p - 256; fill_words(p, *(size_t*)q, 0xFFFFFFFFu); free(q); c->live--; }
 inline int upload_async_staged(nx_ctx*, void* d, const void* h, size_t n) { memcpy(d, h, n); return NX_OK; }
 inline int copy_d2h_blocking(nx_ctx*, void* h, const void* d, size_t n) { memcpy(h, d, n); return NX_OK; }
 

@@ -145,11 +145,15 @@ struct DeviceGuard { explicit DeviceGuard(const nx_ctx*) {} };
 #define NX_GUARD(c) nx::DeviceGuard nx_guard__(c)
 #define NX_TRY(call) do { int rc__ = (call); if (rc__ != NX_OK) return rc__; } while (0)
 // an allocation is exactly as long as asked (not rounded up), so that the sanitizer sees the first word past its end
+// and it never comes zeroed or with a previous owner's plausible words: dev_alloc fills it with 0xA5A5A5A5 (>= p, nonzero), dev_free with
+// 0xFFFFFFFF before the memory goes back
+inline void fill_bytes(void* p, size_t bytes, u32 w) { for (size_t i = 0; i < bytes; i++) ((unsigned char*)p)[i] = (unsigned char)(w >> (8 * (i & 3))); }
 inline int dev_alloc(nx_ctx* c, size_t bytes, void** out) {
     size_t* p = (size_t*)malloc(bytes + 256); p[0] = bytes; *out = (char*)p + 256;
+    fill_bytes(*out, bytes, 0xA5A5A5A5u);
     c->live++; c->live_bytes += bytes; c->peak_bytes = std::max(c->peak_bytes, c->live_bytes); return NX_OK;
 }
-inline void dev_free(nx_ctx* c, void* p) { size_t* q = (size_t*)((char*)p - 256); c->live--; c->live_bytes -= q[0]; free(q); }
+inline void dev_free(nx_ctx* c, void* p) { size_t* q = (size_t*)((char*)p - 256); c->live--; c->live_bytes -= q[0]; fill_bytes(p, q[0], 0xFFFFFFFFu); free(q); }
 inline int upload_async_staged(nx_ctx*, void* d, const void* h, size_t n) { memcpy(d, h, n); return NX_OK; }
 inline int copy_d2h_blocking(nx_ctx*, void* h, const void* d, size_t n) { memcpy(h, d, n); return NX_OK; }
 #define hipLaunchKernelGGL(k, g, b, sh, st, ...) emu::launch((g), (b), [=]() { k(__VA_ARGS__); })

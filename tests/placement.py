@@ -395,7 +395,7 @@ def _leaf_chain(log, sh, rng, variant):
     return p
 
 
-@entry("nx_merkle_from_leaves", "merkle", "B", ("merkle.hip:1174 nx_copy of the digests", "ctx.hip:511 nx_copy: copy_kernel (uint4) or hipMemcpyAsync"),
+@entry("nx_merkle_from_leaves", "merkle", "B", ("merkle.hip:1174 nx_copy of the digests", "ctx.hip:555 nx_copy: copy_kernel (uint4) or hipMemcpyAsync"),
        sizes=(0, 1, 2, 3, 5, 6), vector_from="every size (8 words per digest: n_words & 3 == 0), decided by the pointer alone")
 def _from_leaves(log, sh, rng, variant):
     mode = 1 if "raw0" in variant else 0
@@ -556,7 +556,7 @@ def _inv_qm31(log, sh, rng, variant):
     return p
 
 
-@entry("nx_m31_add_into", "field", "S", ("ctx.hip:242 m31_add_into_kernel: words",), sizes=range(len(ODD_SIZES)))
+@entry("nx_m31_add_into", "field", "S", ("ctx.hip:275 m31_add_into_kernel: words",), sizes=range(len(ODD_SIZES)))
 def _add_into(log, sh, rng, variant):
     n = ODD_SIZES[log]
     p = Plan(n=n)
@@ -567,8 +567,8 @@ def _add_into(log, sh, rng, variant):
     return p
 
 
-@entry("nx_m31_widen", "field", "W", ("ctx.hip:244 m31_widen_kernel: u64 stores, src words", "ctx.hip:245"), sizes=range(len(ODD_SIZES)),
-       wide=[("d_dst", 8, "ctx.hip:244", None)], note="src (word access) is shifted; dst at 0 or 2 words")
+@entry("nx_m31_widen", "field", "W", ("ctx.hip:277 m31_widen_kernel: u64 stores, src words", "ctx.hip:278"), sizes=range(len(ODD_SIZES)),
+       wide=[("d_dst", 8, "ctx.hip:277", None)], note="src (word access) is shifted; dst at 0 or 2 words")
 def _widen(log, sh, rng, variant):
     n = ODD_SIZES[log]
     p = Plan(n=n)
@@ -579,8 +579,8 @@ def _widen(log, sh, rng, variant):
     return p
 
 
-@entry("nx_m31_narrow", "field", "W", ("ctx.hip:247 m31_narrow_kernel: u64 loads, dst words", "ctx.hip:248"), sizes=range(len(ODD_SIZES)),
-       wide=[("d_src", 8, "ctx.hip:247", None)], note="dst (word access) is shifted; src at 0 or 2 words; sums of up to 2^33 p reduced mod p")
+@entry("nx_m31_narrow", "field", "W", ("ctx.hip:280 m31_narrow_kernel: u64 loads, dst words", "ctx.hip:281"), sizes=range(len(ODD_SIZES)),
+       wide=[("d_src", 8, "ctx.hip:280", None)], note="dst (word access) is shifted; src at 0 or 2 words; sums of up to 2^33 p reduced mod p")
 def _narrow(log, sh, rng, variant):
     n = ODD_SIZES[log]
     p = Plan(n=n)
@@ -676,8 +676,8 @@ def _upload_narrow(log, sh, rng, variant):
 COPY_SIZES = (1, 3, 4, 8, 64, 257, 1024)
 
 
-@entry("nx_copy", "layout", "B", ("ctx.hip:511 (n_words & 3) or a misaligned pointer: hipMemcpyAsync", "ctx.hip:237 else copy_kernel (uint4)"), sizes=range(len(COPY_SIZES)),
-       vector_from="every multiple of 4 words (n_words & 3 == 0)", note="sizes are word counts COPY_SIZES[log]; copy_columns (ctx.hip:293-295: n_cols >= 4, the same test of the pointers) is internal: the existing host-commit tests reach it")
+@entry("nx_copy", "layout", "B", ("ctx.hip:555 (n_words & 3) or a misaligned pointer: hipMemcpyAsync", "ctx.hip:270 else copy_kernel (uint4)"), sizes=range(len(COPY_SIZES)),
+       vector_from="every multiple of 4 words (n_words & 3 == 0)", note="sizes are word counts COPY_SIZES[log]; copy_columns (ctx.hip:326-328: n_cols >= 4, the same test of the pointers) is internal: the existing host-commit tests reach it")
 def _copy(log, sh, rng, variant):
     n = COPY_SIZES[log]
     p = Plan(n=n)
@@ -879,7 +879,7 @@ def _logup_program(log, sh, rng, variant):
 MULT_TILE_LOG = 12     # multiplicity.hip:27 MULT_TILE = 4096 rows
 
 
-@entry("nx_logup_multiplicities", "logup", "B", ("multiplicity.hip:254 vec = n >= MULT_TILE && aligned", "internal.h:195 gld4_guarded", "multiplicity.hip:61", "multiplicity.hip:173 table / d_mult: words"),
+@entry("nx_logup_multiplicities", "logup", "B", ("multiplicity.hip:254 vec = n >= MULT_TILE && aligned", "internal.h:198 gld4_guarded", "multiplicity.hip:61", "multiplicity.hip:173 table / d_mult: words"),
        sizes=(0, 1, 3, 6, MULT_TILE_LOG), vector_from="2^12 rows of a use (MULT_TILE)")
 def _multiplicities(log, sh, rng, variant):
     log_table, n = 4, 1 << log

@@ -110,7 +110,7 @@ def test_the_dispatch_thresholds_are_the_sources():
     assert "SC_MIN_LOG = SC_H + SC_T + 1" in source_line("logup.hip:293") and "SC_H = 7, SC_T = 5" in source_line("logup.hip:293") and PL.SCAN_TILED_LOG == 13
     assert "n >= 4 && !(align & 15)" in source_line("access_history.cuh:532")
     assert "n >= per_lane && !((uintptr_t)d_cols[c] & 15)" in source_line("fft.hip:783")
-    assert "(n_words & 3) || ((uintptr_t)d_dst & 15) || ((uintptr_t)d_src & 15)" in source_line("ctx.hip:511")
+    assert "(n_words & 3) || ((uintptr_t)d_dst & 15) || ((uintptr_t)d_src & 15)" in source_line("ctx.hip:555")
     assert "& 15)) vec4 = false" in source_line("air_jit.hip:1603")
     assert "aligned16 && ((uintptr_t)sorted[i] & 15u) == 0" in source_line("merkle.hip:995")
     assert "EVAL_LOG_LO = 10" in source_line("pcs.hip:19")
