@@ -113,6 +113,31 @@ int nx_ctx_set_hash_mode(nx_ctx* ctx, int mode);
  * constants is filled when the option turns on and again where it wraps) and "debug.poison_free" (1, with "debug.poison" != 0: a block is
  * filled again when it goes back to the cache).  Code that reads a temporary before it wrote all of it, or frees a block something
  * still reads, then computes from the pattern instead of from zero pages or a previous call's values.
+ * The device-memory budget of the context's block allocator (nx_alloc and every internal buffer): "mem.limit_bytes" (0 .. 2^62; 0, the
+ * default, = none; NX_MEM_LIMIT_BYTES) bounds the bytes the context holds from the driver as blocks, live + cached.  A request of b bytes
+ * (rounded up to 256) that no cached block of its size serves first gives the cache back to the driver when live + cached + b would pass
+ * the limit; a request with live + b over the limit — cached block or not — is NX_ERR_OOM before any driver call, and nx_last_error names
+ * the request, the live bytes and the limit ("dev_alloc: 16777216 bytes refused: 33554432 live of a budget of 41943040
+ * (mem.limit_bytes)").  A limit below the current live count is accepted and refuses later requests only.  NOT blocks, and not counted:
+ * the context's fixed buffers — the staging ring of pointer tables and constants (16 MiB of device memory and its 16 MiB pinned host
+ * mirror, from nx_ctx_create on), the bounce buffer of the blocking copies (2 x 4 MiB pinned host memory, from the first copy of >= 32 KiB
+ * on) and the pack ring of the narrow upload (pinned host memory, two slots of 16 columns x 2^log_size rows x 2 bytes, from the first
+ * packed column until nx_ctx_trim).  "mem.cache_bytes" (0 .. 2^62; default 192 GiB, NX_MEM_CACHE_BYTES): the most bytes of freed blocks
+ * kept for reuse; a free that takes the cache beyond it hands the whole cache back to the driver, which synchronises the context as
+ * nx_ctx_trim does; 0 = every freed block goes back at once.  "mem.cached_bytes" (read-only): the bytes of freed blocks held now.
+ * "debug.fail_alloc" (n >= 1; default 0): the n-th request the allocator sees from now on is refused once with NX_ERR_OOM ("debug.fail_alloc:
+ * request n (B bytes) refused"), decided on the host before any driver call, and the option is 0 again; "debug.alloc_count" (read-only:
+ * setting it is NX_ERR_ARG) is the number of requests the allocator has seen since nx_ctx_create — the difference around a call is the
+ * number of positions a sweep of that call has to visit.
+ *
+ * AFTER NX_ERR_OOM — the rule of every entry of this header that takes a context or a handle made from one, whatever refused the
+ * request (the driver, "mem.limit_bytes", "debug.fail_alloc"): (1) nx_ctx_memory's live count is what it was before the call: every
+ * block the call took has gone back to the cache, in the order the success path returns them; (2) every *out handle is NULL: no
+ * nx_tree, nx_twiddles, nx_trace_partition, nx_air_kernel, nx_prover or shared tree is left half-made, and output columns of the caller hold
+ * unspecified words; (3) a session (nx_prover) is in the state documented for the refused narrow upload: the transcript is untouched, a
+ * begun tree is no longer begun and may be begun again, a failed nx_prover_prove has restored the channel; (4) the context stays usable:
+ * the same call repeated returns the words it always returns; (5) a row-sharded prove aborts its transport (nx_comm.abort) so that no
+ * peer waits out "comm.timeout_ms": after nx_comm_group_reset (or a new communicator) the group proves again.
  * Unknown names and out-of-range values are NX_ERR_ARG.
  * None of them changes a result: proofs, roots and transforms are bit-identical under every setting. */
 int nx_ctx_set_option(nx_ctx* ctx, const char* name, int64_t value);

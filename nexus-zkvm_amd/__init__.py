@@ -984,7 +984,10 @@ class HipBackend:
 
     def set_option(self, name, value):
         """Per-context policy / tuning (nx_ctx_set_option): "fft.batch_cols", "fft.streams",
-        "fri.dist_min_log", "dist.chunks", "air.segment", ...  The NX_* environment variables only seed a new context's defaults."""
+        "fri.dist_min_log", "dist.chunks", "air.segment", ...  The NX_* environment variables only seed a new context's defaults.
+        The device-memory budget: "mem.limit_bytes" (0 = none; a request beyond it raises with NX_ERR_OOM, nothing left behind),
+        "mem.cache_bytes" (most bytes of freed blocks kept); debug aids: "debug.fail_alloc" = n refuses the n-th following allocator
+        request once; get_option("debug.alloc_count") / ("mem.cached_bytes") are read-only."""
         self._chk(self.L.nx_ctx_set_option(self.ctx, name.encode(), C.c_int64(int(value))))
 
     def get_option(self, name):

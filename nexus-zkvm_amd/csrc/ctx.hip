@@ -183,7 +183,7 @@ static int dev_alloc_poisoned(nx_ctx* ctx, size_t bytes, void** out) {
 
 int dev_alloc(nx_ctx* ctx, size_t bytes, void** out) {
     if (bytes == 0) bytes = 4;
-    bytes = (bytes + 255) & ~(size_t)255;
+    bytes = (bytes + 255) & ~(size_t)255; { const int rc = dev_alloc_admit(ctx, bytes, out); if (rc != NX_OK) return rc; }      // mem.hip: counted; refused on the host when the injection or the budget says so
     auto it = ctx->free_blocks.find(bytes);
     if (it != ctx->free_blocks.end()) {
         *out = it->second; ctx->free_blocks.erase(it); ctx->cached_bytes -= bytes;
@@ -191,7 +191,7 @@ int dev_alloc(nx_ctx* ctx, size_t bytes, void** out) {
         ctx->live_bytes += bytes; ctx->peak_live_bytes = std::max(ctx->peak_live_bytes, ctx->live_bytes);
         return ctx->opt.debug_poison ? dev_alloc_poisoned(ctx, bytes, out) : NX_OK;
     }
-    hipError_t e = hipMalloc(out, bytes);
+    dev_alloc_make_room(ctx, bytes); hipError_t e = hipMalloc(out, bytes);
     if (e == hipErrorOutOfMemory) {  // give cached blocks back to the driver and retry once
         (void)hipGetLastError();
         dev_cache_release(ctx);
@@ -211,7 +211,7 @@ void dev_free(nx_ctx* ctx, void* p) {
     ctx->cached_bytes += it->second;
     ctx->live_bytes -= it->second;
     ctx->live_blocks.erase(it);
-    if (ctx->cached_bytes > ((size_t)192 << 30)) dev_cache_release(ctx);  // keep the cache bounded (a 2^24-row prove recycles ~100 GB)
+    if (ctx->cached_bytes > ctx->opt.mem_cache_bytes) dev_cache_release(ctx);  // "mem.cache_bytes": keep the cache bounded (default NX_MEM_CACHE_BYTES_DEFAULT)
 }
 void dev_cache_release(nx_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
@@ -374,7 +374,7 @@ static nx_options options_from_env() {
     o.machine_logup_program = env_int("NX_MACHINE_LOGUP_PROGRAM", 0) != 0;
     o.trace_vec4 = env_int("NX_TRACE_VEC4", 1) != 0;   // profiles/trace_program_bench.json: 0.180 ms against 0.196 ms for 41 columns of 2^22 rows
     o.debug_poison = clampi(env_int("NX_DEBUG_POISON", 0), 0, 3);
-    o.debug_poison_free = env_int("NX_DEBUG_POISON_FREE", 0) != 0;
+    o.debug_poison_free = env_int("NX_DEBUG_POISON_FREE", 0) != 0; mem_options_from_env(&o);
     o.host_pack_threads = clampi((int)std::thread::hardware_concurrency(), 1, 16);   // a GPU box grants a command 16 CPUs
     return o;
 }
@@ -408,7 +408,7 @@ static const OptEntry k_options[] = {
     {"debug.poison_free", &nx_options::debug_poison_free, 0, 1},
 };
 int nx_ctx_set_option(nx_ctx* ctx, const char* name, int64_t value) {
-    if (!ctx || !name) return set_err(ctx, NX_ERR_ARG, "nx_ctx_set_option: NULL argument");
+    if (!ctx || !name) return set_err(ctx, NX_ERR_ARG, "nx_ctx_set_option: NULL argument"); { int rc = NX_OK; if (mem_option_set(ctx, name, value, &rc)) return rc; }
     for (const OptEntry& e : k_options)
         if (!strcmp(e.name, name)) {
             if (value < e.lo || value > e.hi) return set_err(ctx, NX_ERR_ARG, std::string("nx_ctx_set_option: value out of range for ") + name);
@@ -424,7 +424,7 @@ int nx_ctx_set_option(nx_ctx* ctx, const char* name, int64_t value) {
     return set_err(ctx, NX_ERR_ARG, std::string("nx_ctx_set_option: unknown option ") + name);
 }
 int nx_ctx_get_option(const nx_ctx* ctx, const char* name, int64_t* value) {
-    if (!ctx || !name || !value) return set_err(const_cast<nx_ctx*>(ctx), NX_ERR_ARG, "nx_ctx_get_option: NULL argument");
+    if (!ctx || !name || !value) return set_err(const_cast<nx_ctx*>(ctx), NX_ERR_ARG, "nx_ctx_get_option: NULL argument"); if (mem_option_get(ctx, name, value)) return NX_OK;
     for (const OptEntry& e : k_options)
         if (!strcmp(e.name, name)) { *value = ctx->opt.*(e.field); return NX_OK; }
     return set_err(const_cast<nx_ctx*>(ctx), NX_ERR_ARG, std::string("nx_ctx_get_option: unknown option ") + name);

@@ -506,7 +506,7 @@ extern "C" {
 
 int nx_twiddles_create(nx_ctx* ctx, uint32_t log_half_coset, nx_twiddles** out) {
     NX_GUARD(ctx);
-    if (!ctx || !out) return set_err(ctx, NX_ERR_ARG, "nx_twiddles_create: NULL argument");
+    if (!ctx || !out) return set_err(ctx, NX_ERR_ARG, "nx_twiddles_create: NULL argument"); *out = nullptr;
     if (log_half_coset < 1 || log_half_coset > 28) return set_err(ctx, NX_ERR_ARG, "nx_twiddles_create: log_half_coset out of range [1,28]");
     nx_twiddles* t = new nx_twiddles();
     t->ctx = ctx; t->log_half = log_half_coset; t->d_tw = nullptr; t->d_itw = nullptr; t->d_tw2 = nullptr; t->d_itw2 = nullptr;

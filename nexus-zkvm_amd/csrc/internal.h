@@ -40,7 +40,7 @@ struct nx_options {
     int host_pack_threads;        // "host.pack_threads": host threads that pack NX_COL_U32_AS_* columns (HostFeed)
     // debug aids of the caching allocator ("poisoned blocks"); with both 0 dev_alloc / dev_free take one extra branch
     int debug_poison;             // "debug.poison": 0 = off; 1, 2, 3: dev_alloc fills the whole rounded block, fresh or recycled, with 0xA5A5A5A5 / 0xFFFFFFFF / 0x00000001 on ctx->cur before it returns it; the staging ring is filled when the option turns on and at every wrap
-    int debug_poison_free;        // "debug.poison_free": while debug.poison != 0, dev_free fills a block it owns with the same pattern before it caches it
+    int debug_poison_free; size_t mem_limit_bytes, mem_cache_bytes; int debug_fail_alloc;        // "debug.poison_free": while debug.poison != 0, dev_free fills a block it owns with the same pattern before it caches it; "mem.limit_bytes" (0 = none: most bytes held from the driver as blocks, live + cached), "mem.cache_bytes" (most bytes of freed blocks kept), "debug.fail_alloc" (n: the n-th following request is refused once): the budget and the injection of mem.hip, described in the context section of include/nexus_hip.h
 };
 
 struct nx_ctx {
@@ -75,7 +75,7 @@ struct nx_ctx {
     std::multimap<size_t, void*> free_blocks;
     std::map<void*, size_t> live_blocks;
     size_t cached_bytes;
-    size_t live_bytes = 0, peak_live_bytes = 0;      // sum of live_blocks and its high-water mark since the last reset (nx_ctx_memory)
+    uint64_t alloc_count = 0, fail_alloc_seen = 0; size_t live_bytes = 0, peak_live_bytes = 0;      // "debug.alloc_count": requests dev_alloc has seen, and those seen since "debug.fail_alloc" was armed; sum of live_blocks and its high-water mark since the last reset (nx_ctx_memory)
     // pinned host blocks cached by exact size: targets of asynchronous device-to-host copies that must outlive later stage() calls
     // (the partial sums of every OODS request of a proof are collected after ONE synchronisation)
     std::multimap<size_t, void*> free_pinned;
@@ -94,9 +94,9 @@ struct nx_ctx {
     // is an input error, not a reason to re-bootstrap a prover farm's communicator.
     bool symmetric_failure = false;
     // Set by the first collective a sharded prove of this context enters (Dist::allgather_host / allgather_dev / alltoallv), cleared by the
-    // entry point.  While it is false no peer can be waiting for this rank, so a refusal needs no transport abort; once it is true every
-    // failure that is not symmetric aborts — also NX_ERR_ARG, which stage(), TreeBuilder, nx_logup_cols* and air_eval_rows can return from
-    // deep inside a prove, on one rank only.
+    // entry point.  While it is false only NX_ERR_ARG (the argument checks, which every rank fails alike) needs no transport abort: any other failure there
+    // (NX_ERR_OOM or a HIP error in nx_twiddles_create, a slab, stage_tree) is one-sided and the peers already wait in the vote's all-gather.  Once it is true every failure
+    // that is not symmetric aborts — also NX_ERR_ARG, which stage(), TreeBuilder, nx_logup_cols* and air_eval_rows return from deep inside a prove, on one rank only.
     bool comm_entered = false;
     // "machine.reuse_preprocessed": committed preprocessed trees by statement shape (nxhip::CommitmentTreeProver, type-erased here)
     std::map<std::string, std::shared_ptr<void>> machine_pre_cache;
@@ -237,6 +237,15 @@ int eval_at_points_collect(nx_ctx* ctx, std::vector<EvalJob>* jobs);
 int dev_alloc(nx_ctx* ctx, size_t bytes, void** out);
 void dev_free(nx_ctx* ctx, void* p);
 void dev_cache_release(nx_ctx* ctx);
+// mem.hip: the budget of the allocator ("mem.limit_bytes", "mem.cache_bytes") and the refusal injection ("debug.fail_alloc", "debug.alloc_count").
+// dev_alloc_admit: counts the request and refuses it on the host — NX_ERR_OOM, *out NULL — when the injection is due or the live blocks leave
+// no room under the limit; dev_alloc_make_room: ahead of a driver call, the cache goes back when live + cached + bytes would pass the limit.
+constexpr size_t NX_MEM_CACHE_BYTES_DEFAULT = (size_t)192 << 30;      // a 2^24-row prove recycles ~100 GB
+int dev_alloc_admit(nx_ctx* ctx, size_t bytes, void** out);
+void dev_alloc_make_room(nx_ctx* ctx, size_t bytes);
+void mem_options_from_env(nx_options* o);
+bool mem_option_set(nx_ctx* ctx, const char* name, int64_t value, int* rc);        // true: the name is one of mem.hip's, *rc is the entry's return
+bool mem_option_get(const nx_ctx* ctx, const char* name, int64_t* value);
 // "debug.poison": the word dev_alloc / dev_free / the staging ring are filled with (pattern 1..3)
 inline uint32_t poison_word(int pattern) { return pattern == 1 ? 0xA5A5A5A5u : pattern == 2 ? 0xFFFFFFFFu : 0x00000001u; }
 

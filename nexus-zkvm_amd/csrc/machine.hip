@@ -825,11 +825,13 @@ using namespace nx;
 
 // A rank whose sharded prove failed leaves its peers waiting in the next collective: tell the transport (nx_comm.abort, optional)
 // — unless the failure is one every rank reached by itself (ctx->symmetric_failure: the vote, ConstraintsNotSatisfied) or one returned
-// before this rank entered its first collective (ctx->comm_entered false: the argument checks ahead of dist_init and the vote — no peer
-// waits for a rank that never joined): an abort cannot be undone, and an invalid trace must not cost a prover farm its group.  The
-// error CODE does not decide: NX_ERR_ARG also comes from deep inside a sharded prove, one-sided.
+// before this rank entered its first collective with NX_ERR_ARG (ctx->comm_entered false: the argument checks ahead of dist_init and the
+// vote, which every rank fails alike): an abort cannot be undone, and an invalid trace must not cost a prover farm its group.  Any other
+// failure before the first collective (NX_ERR_OOM or a HIP error in nx_twiddles_create, a slab, stage_tree) is one-sided: the peers are
+// already in the vote's all-gather and would wait out "comm.timeout_ms".  Once a collective was entered the error CODE does not decide:
+// NX_ERR_ARG also comes from deep inside a sharded prove, one-sided.
 static void abort_peers(nx_ctx* ctx, const nx_comm* comm, int rc) {
-    if (rc != NX_OK && ctx->comm_entered && !ctx->symmetric_failure && comm && comm->world > 1 && comm->abort) comm->abort(comm->user);
+    if (rc != NX_OK && !ctx->symmetric_failure && (ctx->comm_entered || rc != NX_ERR_ARG) && comm && comm->world > 1 && comm->abort) comm->abort(comm->user);
 }
 
 static int hand_out(nx_ctx* ctx, int rc, std::vector<uint32_t>& w, uint32_t** proof_words, size_t* n_words, const char* who) {

@@ -981,7 +981,7 @@ extern "C" {
 
 int nx_merkle_commit(nx_ctx* ctx, const uint32_t* const* d_cols, const uint32_t* log_sizes, uint32_t n_cols, nx_tree** out) {
     NX_GUARD(ctx);
-    if (!ctx || !out) return set_err(ctx, NX_ERR_ARG, "nx_merkle_commit: NULL argument");
+    if (!ctx || !out) return set_err(ctx, NX_ERR_ARG, "nx_merkle_commit: NULL argument"); *out = nullptr;
     // stable sort by size, descending (MerkleProver::commit)
     std::vector<uint32_t> order(n_cols);
     std::iota(order.begin(), order.end(), 0u);
@@ -1162,7 +1162,7 @@ int nx_merkle_leaf_chain(nx_ctx* ctx, const uint32_t* const* d_cols, uint32_t n_
 
 int nx_merkle_from_leaves(nx_ctx* ctx, const uint32_t* d_leaf_digests, uint32_t log_size, nx_tree** out) {
     NX_GUARD(ctx);
-    if (!ctx || !out || !d_leaf_digests) return set_err(ctx, NX_ERR_ARG, "nx_merkle_from_leaves: NULL argument");
+    if (!ctx || !out || !d_leaf_digests) return set_err(ctx, NX_ERR_ARG, "nx_merkle_from_leaves: NULL argument"); *out = nullptr;
     if (log_size > 30) return set_err(ctx, NX_ERR_ARG, "nx_merkle_from_leaves: layer too large");
     nx_tree* t = new nx_tree();
     t->ctx = ctx;

@@ -1097,7 +1097,7 @@ int prove_core(nx_ctx* ctx, CommitmentSchemeProver& cs, Blake2sChannel& channel,
                 }
             }
             pd.out.assign(4 * pidx.size(), 0);
-            H_TRY(eval_at_points_enqueue(ctx, pp.data(), kv.first, pidx.data(), pts.data(), (uint32_t)pidx.size(), pd.out.data(), &jobs));
+            const int rc_enq = eval_at_points_enqueue(ctx, pp.data(), kv.first, pidx.data(), pts.data(), (uint32_t)pidx.size(), pd.out.data(), &jobs); if (rc_enq != NX_OK) { (void)eval_at_points_collect(ctx, &jobs); return rc_enq; }      // the jobs queued so far own their blocks: drained and given back, as on success
         }
         hs_enq.stop();
         { HostSpan hs("pc.oods collect (sync)"); H_TRY(eval_at_points_collect(ctx, &jobs)); }
@@ -1877,6 +1877,7 @@ int nx_plan_local_columns(const uint32_t* group_n_cols, const uint32_t* group_lo
 int nx_prover_create(nx_ctx* ctx, const nx_pcs_config* cfg, uint32_t max_log_size, nx_prover** out) {
     NX_GUARD(ctx);
     if (!ctx || !cfg || !out) return set_err(ctx, NX_ERR_ARG, "nx_prover_create: NULL argument");
+    *out = nullptr;
     if (cfg->log_blowup < 1 || cfg->log_constraint_degree < 1 || cfg->log_constraint_degree > 2 || max_log_size < 1 || max_log_size + cfg->log_constraint_degree + cfg->log_blowup > 31)
         return set_err(ctx, NX_ERR_ARG, "nx_prover_create: log_blowup >= 1, log_constraint_degree in {1,2}, 1 <= max_log_size required");
     NX_TRY(nx_ctx_set_hash_mode(ctx, (int)cfg->hash_mode));
@@ -1951,7 +1952,7 @@ int nx_prover_tree_begin(nx_prover* p, const uint32_t* log_sizes, uint32_t n_col
         nx_prover::Run r; r.n_cols = j - i; r.log = log_sizes[i];
         r.lo = nxhip::Dist::cut(r.n_cols, D.rank, D.world); r.hi = nxhip::Dist::cut(r.n_cols, D.rank + 1, D.world);
         int rc = r.slab.alloc(p->ctx, (size_t)std::max<uint32_t>(r.hi - r.lo, 1) << r.log);
-        if (rc != NX_OK) { p->pending.clear(); return rc; }
+        if (rc != NX_OK) { p->pending.clear(); for (uint32_t k = 0; k < n_cols; k++) d_cols_out[k] = nullptr; return rc; }      // no pointer into a slab that went back
         for (uint32_t k = 0; k < r.n_cols; k++) d_cols_out[i + k] = (k >= r.lo && k < r.hi) ? r.slab.p + ((size_t)(k - r.lo) << r.log) : nullptr;
         p->pending.push_back(std::move(r));
         i = j;

@@ -135,6 +135,7 @@ int nx_trace_partition_create(nx_ctx* ctx, const uint32_t* d_class, uint32_t n_s
     if (n_steps > TP_MAX_STEPS) return set_err(ctx, NX_ERR_ARG, who + ": n_steps of " + std::to_string(n_steps) + ", at most 2^30");
     if (n_steps && !d_class) return set_err(ctx, NX_ERR_ARG, who + ": NULL d_class with n_steps of " + std::to_string(n_steps));
     if (!ctx) return set_err(ctx, NX_ERR_ARG, who + ": NULL context");
+    *out = nullptr;
 
     std::unique_ptr<nx_partition> p(new nx_partition());
     p->ctx = ctx; p->d_class = d_class; p->n_steps = n_steps; p->n_classes = n_classes; p->d_order = nullptr;

@@ -582,6 +582,9 @@ impl Session {
     pub fn ctx(&self) -> *mut sys::nx_ctx { self.ctx }
     /// Per-context policy (include/nexus_hip.h `nx_ctx_set_option`), e.g. `("air.degree_split", 0)` to evaluate every constraint on the
     /// component's full domain like Stwo does.  No option changes a proof byte.  An unknown name or a value out of range is `Err(Argument)`.
+    /// The device-memory budget of a context that shares its card: `("mem.limit_bytes", b)` (0 = none) bounds the bytes it holds from the
+    /// driver as blocks, `("mem.cache_bytes", b)` the freed blocks it keeps; a request beyond the limit is `NX_ERR_OOM` with every buffer of
+    /// the call released and the session usable.  `("debug.fail_alloc", n)` refuses the n-th following allocator request once.
     pub fn set_option(&mut self, name: &str, value: i64) -> Result<(), HipError> {
         let c = std::ffi::CString::new(name).map_err(|_| HipError::Argument("option name holds a NUL byte".into()))?;
         try_check(self.ctx, unsafe { sys::nx_ctx_set_option(self.ctx, c.as_ptr(), value) })
